@@ -18,9 +18,14 @@ Workloads (--workload):
   msm              configs[2]: 2^20-point MSM over the alpha = 12345 SRS (weak scaling).
   ntt4, msm-shard  configs[4]: 2^26 four-step DFT (one all_to_all) and 2^24-point MSM split by
                    point range (strong scaling).
-Inputs are synthetic, resident in HBM before the timed region.
+Inputs are synthetic, resident in HBM before the timed region, and the same from run to run.
 
-Also reported:
+A plain run sets up, warms up, times the K steps and prints the line; `roofline`, `gpu_sclk`, the
+clock probe and `cpu_baseline` are null in it.  `--dump-outputs DIR` also writes what the last timed
+step returned as DIR/<name>.npy (dump_outputs below).  `--full` adds everything that takes work of
+its own beside the headline figure.
+
+Reported with --full:
   roofline     -- for the dominant kernel (largest total time): algorithmic bytes per launch
                    / average launch duration (HIP events on the launch
                   stream, eon_ctx_profile, over serialized profiled steps after the timed region)
@@ -33,6 +38,7 @@ Also reported:
   gpu_clock_inkernel_mhz -- the shader clock held under a product chain right after the timed
                   region (eon_diag_clock_probe: s_memtime / s_memrealtime), beside `gpu_sclk`
                   (sysfs, which is not the in-kernel clock).
+  gpu_sclk     -- the sysfs shader clock sampled in a background thread during the timed steps.
   cpu_baseline -- the C restatement (oracle/eon_oracle.c, OpenMP) of the same work timed on this
                   host on a bounded sample, rank 0 at N = 1 only.
 """
@@ -73,6 +79,51 @@ FR_P = [0x43E1F593F0000001, 0x2833E84879B97091, 0xB85045B68181585D, 0x30644E72E1
 def _sig(x: float, n: int = 4) -> float:
     """x to n significant figures (a latency-bound workload's GB/s is far below 0.01)."""
     return float(f"{x:.{n}g}")
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20240
+
+
+def dump_outputs(outs: dict, directory: Path) -> dict:
+    """--dump-outputs: every array of `outs` (what the last timed step returned to its caller: host
+    uint64 limb arrays or int64 device tensors) as directory/<name>.npy in float64.  Each 64-bit
+    word is written as its two 32-bit halves (low, high), which float64 holds exactly, so two
+    builds compare equal element for element.  An array whose share of DUMP_LIMIT_BYTES would be
+    exceeded is cut to a fixed, seeded sample of its rows (first axis, in ascending order)."""
+    directory.mkdir(parents=True, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(outs), 1)
+    written = {}
+    for name, a in outs.items():
+        if not hasattr(a, "shape") or len(a.shape) == 0:
+            a = np.asarray(a).reshape(1)
+        rows = int(a.shape[0])
+        words_per_row = 1
+        for d in a.shape[1:]:
+            words_per_row *= int(d)
+        keep = max(1, share // (16 * words_per_row))  # 2 float64 per 64-bit word
+        if rows > keep:
+            idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(rows, keep, replace=False))
+            if isinstance(a, np.ndarray):
+                a = a[idx]
+            else:
+                import torch
+
+                a = a[torch.from_numpy(idx).to(a.device)]
+        if not isinstance(a, np.ndarray):
+            a = a.cpu().numpy()
+        a = np.ascontiguousarray(a)
+        if a.dtype in (np.int64, np.uint64):
+            a = a.view(np.uint32)
+        a = a.astype(np.float64)
+        np.save(directory / f"{name}.npy", a)
+        written[name] = list(a.shape)
+    return written
+
+
+def fr_limbs(v: int) -> np.ndarray:
+    """A canonical integer as four uint64 limbs (the transcript's alpha / zeta in the dump)."""
+    return np.array([(v >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
 
 
 def synthetic_fr(rows: int, cols: int, seed: int) -> np.ndarray:
@@ -248,6 +299,9 @@ class LdeWorkload:
                                               ctypes.c_void_p(self.out.data_ptr()), self.n, self.w,
                                               self.b, ctypes.byref(self.shift), self.order))
 
+    def outputs(self):
+        return {"lde": self.out}
+
     def describe(self, world):
         a = self.args
         return (f"configs[1]: batched LDE NTT, coset_lde_batch 2^{a.log_n} rows x {self.w} cols over "
@@ -308,6 +362,9 @@ class MsmWorkload:
         c = self.ctx
         c.check(c.lib.eon_msm_g1_dev(c.handle, self.bases, ctypes.c_void_p(self.scalars.data_ptr()),
                                      self.n, self.out.ctypes.data_as(ctypes.c_void_p)))
+
+    def outputs(self):
+        return {"msm": self.out}
 
     def describe(self, world):
         return (f"configs[2]: KZG commit MSM, 2^{self.args.log_msm} BN254 G1 SRS points (alpha=12345, "
@@ -532,6 +589,16 @@ class ProveWorkload:
         p = prove_native(self.air, self.pcs, self.trace, self.alpha, self.zeta, collective=self.coll,
                          challenger=ch)
         self.timings.append(p.timings_ms)
+        self.proof = p
+
+    def outputs(self):
+        p = self.proof
+        tr, qo = p.opened
+        return {"trace_commit": p.trace_commit[0], "quotient_commit": np.concatenate(p.quotient_commit),
+                "trace_opened": np.stack(tr.values[0]), "trace_witnesses": np.stack(tr.witnesses[0]),
+                "quotient_opened": np.concatenate([v[0] for v in qo.values]),
+                "quotient_witnesses": np.concatenate([v[0] for v in qo.witnesses]),
+                "alpha": fr_limbs(p.alpha), "zeta": fr_limbs(p.zeta)}
 
     def describe(self, world):
         w = 164 * self.vl
@@ -588,6 +655,9 @@ class QuotientWorkload:
 
     def step(self):
         self.out = self.air.quotient_values(self.lde, self.log_n, self.log_qd, self.alpha)
+
+    def outputs(self):
+        return {"quotient_values": self.out}
 
     def describe(self, world):
         kind = "generic AIR program (k_air_quotient)" if self.args.air == "generic" else "fused kernel (k_p2_quotient)"
@@ -665,8 +735,12 @@ class VerifyWorkload:
         del pw
 
     def step(self):
-        if self.GV.verify_batch(self.com, self.wit, self.val, self.pts, self.g2a, ctx=self.ctx) is not True:
+        self.ok = self.GV.verify_batch(self.com, self.wit, self.val, self.pts, self.g2a, ctx=self.ctx)
+        if self.ok is not True:
             raise SystemExit("verify_batch rejected the configs[3] proof")
+
+    def outputs(self):
+        return {"verified": np.array([1.0 if self.ok is True else 0.0])}
 
     def describe(self, world):
         return (f"N4: KzgPcs::verify_batch of the configs[3] proof's {self.n} openings (1312 trace columns at "
@@ -725,6 +799,9 @@ class FourStepWorkload:
         from plonky3_eon_amd import distributed as D
 
         self.out = D.fourstep_dft(self.ctx, self.local, self.log_n, self.rank, self.world)
+
+    def outputs(self):
+        return {"dft": self.out}
 
     def describe(self, world):
         return (f"configs[4] (i): forward DFT 2^{self.log_n} over BN254 Fr, four-step "
@@ -787,6 +864,9 @@ class MsmShardWorkload:
         else:
             self.out = self.bases.msm(self.scalars.reshape(-1, 4))
 
+    def outputs(self):
+        return {"msm": self.out}
+
     def describe(self, world):
         return (f"configs[4] (ii): MSM 2^{self.args.log_shard_msm} BN254 G1 points split by point range over "
                 f"{world} GPU(s) (2^{self.args.log_shard_msm} / {world} per GPU)", 1, self.n_total,
@@ -848,10 +928,15 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--log-msm", type=int, default=20)
     ap.add_argument("--msm-scalars", choices=["uniform", "small"], default="uniform",
                     help="msm: uniform Fr scalars, or all < 2^64 (kzg/benches/kzg_benches.rs:16-22)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the per-kernel roofline (serialized profiled steps), the "
+                         "sysfs clock sampler, the in-kernel clock probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB)")
     ap.add_argument("--cpu-sample-cols", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-clock-probe", action="store_true",
-                    help="skip the in-kernel clock probe after the timed region (~2 s)")
+                    help="--full without the in-kernel clock probe after the timed region (~2 s)")
     ap.add_argument("--cpu-full", action="store_true",
                     help="prove: also the larger end-to-end CPU restatement runs (2^10 Horner, 2^12; minutes)")
     ap.add_argument("--serial", action="store_true",
@@ -928,114 +1013,14 @@ def self_launch(n: int) -> int:
     return subprocess.call(cmd)
 
 
-def main() -> int:
-    args = make_parser().parse_args()
-    if args.steps is None:
-        args.steps = 3 if args.workload == "prove" else 10
-    if args.warmup is None:
-        args.warmup = 1 if args.workload == "prove" else 3
-    if args.gpus < 1:
-        print(f"bench.py: --gpus must be >= 1 (got {args.gpus})", file=sys.stderr)
-        return 2
-    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        return self_launch(args.gpus)  # before any GPU call: the parent only waits
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        # a run whose rank count differs from --gpus would time the wrong configuration
-        print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
-        return 2
-
-    import torch
-    import torch.distributed as dist
-
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # EON_BENCH_BACKEND=gloo and EON_BENCH_ONE_DEVICE=1 rehearse the N > 1 code path with every
-    # rank on cuda:0 (a one-GPU box); the timings of such a run mean nothing
-    backend = os.environ.get("EON_BENCH_BACKEND", "nccl")
-    local_dev = 0 if os.environ.get("EON_BENCH_ONE_DEVICE") == "1" else local_rank
-    torch.cuda.set_device(local_dev)
-    dev = torch.device("cuda", local_dev)
-    if world > 1:
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=dev)
-        else:
-            dist.init_process_group(backend)
-
-    from plonky3_eon_amd import Context
-
-    ctx = Context(local_dev)
-    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
-    wl = {"lde": LdeWorkload, "msm": MsmWorkload, "prove": ProveWorkload, "ntt4": FourStepWorkload,
-          "msm-shard": MsmShardWorkload, "quotient": QuotientWorkload,
-          "verify": VerifyWorkload}[args.workload](args, ctx, dev, rank)
-
-    if args.serial:
-        ctx.set_serial(True)
-    for _ in range(args.warmup):
-        wl.step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    sclk = SclkSampler(dev).start()
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        wl.step()
-        print(f"step {i}: {(time.perf_counter() - t0) * 1e3:.1f} ms since start", file=sys.stderr, flush=True)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    sclk_stats = sclk.stop()
-    if world > 1:
-        dist.barrier()
-    # per-launch HIP-event timings come from extra steps after the timed region, run in serial
-    # mode (eon_ctx_set_serial: every kernel on the context stream, none on the MSM / opening side
-    # streams), so that each launch's duration is its own and not shared with the kernels of the
-    # other streams -- the same durations `rocprofv3 --kernel-trace` reports for `--serial`
-    # (profiles/r02_*_kernel_stats.csv)
-    prof_steps = max(1, min(args.steps, 2))
-    ctx.set_serial(True)
-    wl.step()  # warm the serial path's workspaces
-    torch.cuda.synchronize()
-    ctx.profile(True)
-    t_p0 = time.perf_counter()
-    for _ in range(prof_steps):
-        wl.step()
-    torch.cuda.synchronize()
-    serial_ms = (time.perf_counter() - t_p0) * 1e3 / prof_steps
-    prof = ctx.profile_report()
-    ctx.profile(False)
-    ctx.set_serial(args.serial)
-    # the clock the chip holds under this VALU load, and the product peak at that clock, measured
-    # now on this box (eon_diag_clock_probe; MI355X_MICROARCH.md DVFS item 6): ~2 s of the
-    # roofline denominator's own product chain, stamped with s_memtime / s_memrealtime
-    clock = None
-    if not args.no_clock_probe:
-        clock = ctx.clock_probe(160, 1024)
-    if world > 1:
-        dist.barrier()
-    elapsed = t1 - t0
-    ranks = None
-    if world > 1:
-        # what each rank ran on and saw, gathered to rank 0: the device ordinal and PCI address
-        # torch reports, the RCCL communicator's own view (ncclCommCount / ncclCommUserRank /
-        # ncclCommCuDevice, and that device's PCI bus id), and the rank's own timings -- so that
-        # the N-GPU line shows N ranks on N distinct GPUs under one N-rank communicator
-        ranks = [None] * world
-        dist.all_gather_object(ranks, rank_evidence(wl, rank, local_rank, dev, elapsed, args.steps, world))
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    ms_per_step = elapsed * 1e3 / args.steps
+def roofline(args, wl, prof, prof_steps, serial_ms, clock, mulmods, workload) -> dict:
+    """--full: the roofline record of the dominant kernel from the serialized profiled steps
+    (`prof`: eon_ctx_profile's per-kernel report), see the module docstring."""
     kname, kst = max(prof.items(), key=lambda kv: kv[1]["total_ms"])
     avg_ms = kst["total_ms"] / kst["launches"]
     bytes_per_launch = kst["alg_bytes"] / kst["launches"]
     achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9
     gpu_total_ms = sum(v["total_ms"] for v in prof.values()) / prof_steps
-    workload, gbatch, seq, par = wl.describe(world)
-    thr, mulmods = wl.throughput(world, ms_per_step)
 
     roof = {
         "bound": "hbm",
@@ -1115,7 +1100,137 @@ def main() -> int:
         roof["bound"] = "valu"
         roof["valu"]["unit"] = "mulmod/s"
         roof["hbm_frac"] = roof["frac"]
+    # PMC traffic of THIS round's build only (tools/gpu_pmc.sh -> profiles/<round>/traffic_*.json,
+    # stamped with the commit it measured); an older round's file describes another build
+    traffic_file = ROOT / "profiles" / TRAFFIC_ROUND / f"traffic_{args.workload}.json"
+    if traffic_file.exists():
+        try:
+            tf = json.loads(traffic_file.read_text())
+            if tf.get("kernel") == kname and tf.get("workload") == workload:
+                roof["traffic"] = tf.get("bytes_per_launch")
+                roof["traffic_source"] = ("%s (commit %s; raw FETCH_SIZE %.3g GB + WRITE_SIZE %.3g GB per launch; "
+                                          "the x2 streaming-read correction is not applied to these gathers)") % (
+                    traffic_file.relative_to(ROOT), tf.get("commit", "?"), tf["fetch_size_kb_per_launch"] * 1024 / 1e9,
+                    tf["write_size_kb_per_launch"] * 1024 / 1e9)
+                if tf.get("bytes_per_launch_x2_streaming"):
+                    roof["traffic_x2_streaming_upper"] = tf["bytes_per_launch_x2_streaming"]
+        except Exception:
+            pass
+    return roof
+
+
+def main() -> int:
+    args = make_parser().parse_args()
+    if args.steps is None:
+        args.steps = 3 if args.workload == "prove" else 10
+    if args.warmup is None:
+        args.warmup = 1 if args.workload == "prove" else 3
+    if args.gpus < 1:
+        print(f"bench.py: --gpus must be >= 1 (got {args.gpus})", file=sys.stderr)
+        return 2
+    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        return self_launch(args.gpus)  # before any GPU call: the parent only waits
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        # a run whose rank count differs from --gpus would time the wrong configuration
+        print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
+        return 2
+
+    import torch
+    import torch.distributed as dist
+
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    # EON_BENCH_BACKEND=gloo and EON_BENCH_ONE_DEVICE=1 rehearse the N > 1 code path with every
+    # rank on cuda:0 (a one-GPU box); the timings of such a run mean nothing
+    backend = os.environ.get("EON_BENCH_BACKEND", "nccl")
+    local_dev = 0 if os.environ.get("EON_BENCH_ONE_DEVICE") == "1" else local_rank
+    torch.cuda.set_device(local_dev)
+    dev = torch.device("cuda", local_dev)
+    if world > 1:
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=dev)
+        else:
+            dist.init_process_group(backend)
+
+    from plonky3_eon_amd import Context
+
+    ctx = Context(local_dev)
+    ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    wl = {"lde": LdeWorkload, "msm": MsmWorkload, "prove": ProveWorkload, "ntt4": FourStepWorkload,
+          "msm-shard": MsmShardWorkload, "quotient": QuotientWorkload,
+          "verify": VerifyWorkload}[args.workload](args, ctx, dev, rank)
+
+    if args.serial:
+        ctx.set_serial(True)
+    for _ in range(args.warmup):
+        wl.step()
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    sclk = SclkSampler(dev).start() if args.full else None
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        wl.step()
+        print(f"step {i}: {(time.perf_counter() - t0) * 1e3:.1f} ms since start", file=sys.stderr, flush=True)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    sclk_stats = sclk.stop() if sclk else None
+    if world > 1:
+        dist.barrier()
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        # what the last timed step returned, before any further step runs
+        dumped = dump_outputs(wl.outputs(), args.dump_outputs)
+    prof = clock = None
+    if args.full:
+        # per-launch HIP-event timings come from extra steps after the timed region, run in serial
+        # mode (eon_ctx_set_serial: every kernel on the context stream, none on the MSM / opening side
+        # streams), so that each launch's duration is its own and not shared with the kernels of the
+        # other streams -- the same durations `rocprofv3 --kernel-trace` reports for `--serial`
+        # (profiles/r02_*_kernel_stats.csv)
+        prof_steps = max(1, min(args.steps, 2))
+        ctx.set_serial(True)
+        wl.step()  # warm the serial path's workspaces
+        torch.cuda.synchronize()
+        ctx.profile(True)
+        t_p0 = time.perf_counter()
+        for _ in range(prof_steps):
+            wl.step()
+        torch.cuda.synchronize()
+        serial_ms = (time.perf_counter() - t_p0) * 1e3 / prof_steps
+        prof = ctx.profile_report()
+        ctx.profile(False)
+        ctx.set_serial(args.serial)
+        # the clock the chip holds under this VALU load, and the product peak at that clock, measured
+        # now on this box (eon_diag_clock_probe; MI355X_MICROARCH.md DVFS item 6): ~2 s of the
+        # roofline denominator's own product chain, stamped with s_memtime / s_memrealtime
+        if not args.no_clock_probe:
+            clock = ctx.clock_probe(160, 1024)
+        if world > 1:
+            dist.barrier()
+    elapsed = t1 - t0
+    ranks = None
+    if world > 1:
+        # what each rank ran on and saw, gathered to rank 0: the device ordinal and PCI address
+        # torch reports, the RCCL communicator's own view (ncclCommCount / ncclCommUserRank /
+        # ncclCommCuDevice, and that device's PCI bus id), and the rank's own timings -- so that
+        # the N-GPU line shows N ranks on N distinct GPUs under one N-rank communicator
+        ranks = [None] * world
+        dist.all_gather_object(ranks, rank_evidence(wl, rank, local_rank, dev, elapsed, args.steps, world))
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    ms_per_step = elapsed * 1e3 / args.steps
+    workload, gbatch, seq, par = wl.describe(world)
+    thr, mulmods = wl.throughput(world, ms_per_step)
+
+    roof = roofline(args, wl, prof, prof_steps, serial_ms, clock, mulmods, workload) if args.full else None
     result = {
+        "full": args.full,
         "metric": METRIC,
         "value": round(ms_per_step, 3),
         "unit": "ms",
@@ -1139,29 +1254,15 @@ def main() -> int:
         "roofline": roof,
         "cpu_baseline": None,
     }
-    # PMC traffic of THIS round's build only (tools/gpu_pmc.sh -> profiles/<round>/traffic_*.json,
-    # stamped with the commit it measured); an older round's file describes another build
-    traffic_file = ROOT / "profiles" / TRAFFIC_ROUND / f"traffic_{args.workload}.json"
-    if traffic_file.exists():
-        try:
-            tf = json.loads(traffic_file.read_text())
-            if tf.get("kernel") == kname and tf.get("workload") == workload:
-                roof["traffic"] = tf.get("bytes_per_launch")
-                roof["traffic_source"] = ("%s (commit %s; raw FETCH_SIZE %.3g GB + WRITE_SIZE %.3g GB per launch; "
-                                          "the x2 streaming-read correction is not applied to these gathers)") % (
-                    traffic_file.relative_to(ROOT), tf.get("commit", "?"), tf["fetch_size_kb_per_launch"] * 1024 / 1e9,
-                    tf["write_size_kb_per_launch"] * 1024 / 1e9)
-                if tf.get("bytes_per_launch_x2_streaming"):
-                    roof["traffic_x2_streaming_upper"] = tf["bytes_per_launch_x2_streaming"]
-        except Exception:
-            pass
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
 
     if ranks is not None:
         result["ranks"] = ranks
         result["distinct_gpus"] = len({r["pci_bus_id"] for r in ranks})
         counts = {r.get("nccl_comm_count") for r in ranks}
         result["rccl_comm_count"] = counts.pop() if len(counts) == 1 else sorted(counts, key=str)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = wl.cpu_baseline()
     if world > 1:
         dist.barrier()

@@ -1,7 +1,9 @@
 """GPU: bench.py keeps its output contract (the driver parses it): exactly one JSON line with the
-required keys, `roofline` (bound / achieved / peak / unit / frac / traffic, frac = achieved / peak)
-and `cpu_baseline` (value / unit / cores / kind / sample).  Runs the quick configs[2] workload and
-a small GPU verify_batch (N4; its single-thread pairing chains report the bound "latency")."""
+required keys; with --full, `roofline` (bound / achieved / peak / unit / frac / traffic, frac =
+achieved / peak) and `cpu_baseline` (value / unit / cores / kind / sample).  Runs the quick
+configs[2] workload and a small GPU verify_batch (N4; its single-thread pairing chains report the
+bound "latency").  A plain run leaves those fields null and, with --dump-outputs, writes what its
+last timed step returned."""
 
 import json
 import subprocess
@@ -17,7 +19,7 @@ ROOT = Path(__file__).resolve().parents[1]
 @pytest.mark.parametrize("extra", [["--workload", "msm"],
                                    ["--workload", "verify", "--log-trace", "6", "--vector-len", "1"]])
 def test_bench_json_contract(extra):
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), *extra, "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), *extra, "--full", "--steps", "3", "--warmup", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -54,7 +56,7 @@ def test_bench_self_launch_ranks(gpus, extra):
 
     env = dict(os.environ, EON_BENCH_BACKEND="gloo", EON_BENCH_ONE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), *extra,
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), *extra, "--full",
                           "--steps", "2", "--warmup", "1"], cwd=ROOT, capture_output=True, text=True, timeout=240,
                          env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -71,3 +73,33 @@ def test_bench_self_launch_ranks(gpus, extra):
     assert max(r["ms_per_step"] for r in ranks) <= d["ms_per_step"] + 1e-3
     if "--workload" not in extra:  # the prove's stages, per rank
         assert all("commit to trace data" in r["stage_ms"] for r in ranks)
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path, gpu_ctx):
+    """A plain run (no --full) times its steps only: the fields of the extra measurements are null,
+    `ms_per_step` is the headline value, and --dump-outputs writes the last timed step's result --
+    here the MSM of the benchmark's own inputs, recomputed through the package -- as float64 halves
+    of each 64-bit limb."""
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from plonky3_eon_amd.msm import MsmBases, srs_powers
+
+    n = 1 << 10
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--workload", "msm", "--log-msm", "10",
+                          "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")],
+                         cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] == d["value"] > 0
+    assert d["unit"] == "ms" and d["higher_is_better"] is False and d["dtype"] and d["metric"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["gpu_clock_probe"] is None
+    assert out.stderr.count("ms since start") == 2  # exactly --steps timed steps
+    got = np.load(tmp_path / "d" / "msm.npy")
+    assert got.dtype == np.float64 and got.shape == (16,) and d["dumped_outputs"] == {"msm": [16]}
+    scalars = bench.synthetic_fr(n, 1, 3).reshape(n, 4)
+    want = MsmBases(srs_powers(n, 12345, gpu_ctx), gpu_ctx, precompute=True).msm(scalars)
+    np.testing.assert_array_equal(got, np.ascontiguousarray(want, dtype=np.uint64).view(np.uint32).astype(np.float64))

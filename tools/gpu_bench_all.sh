@@ -9,7 +9,8 @@ run() {  # name args...
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['ms_per_step'], d['roofline'].get('valu', {}).get('frac'), d['roofline'].get('frac'))" \
     gpurun_out/bench_$n.json $n
 }
-run lde --workload lde && run lde_bitrev --workload lde --order bitrev && run msm --workload msm \
-  && run msm_small --workload msm --msm-scalars small && run ntt4 --workload ntt4 \
-  && run msm_shard --workload msm-shard && run quotient_fused --workload quotient \
-  && run quotient_generic --workload quotient --air generic && run verify --workload verify
+F=--full  # the summary above reads the roofline
+run lde $F --workload lde && run lde_bitrev $F --workload lde --order bitrev && run msm $F --workload msm \
+  && run msm_small $F --workload msm --msm-scalars small && run ntt4 $F --workload ntt4 \
+  && run msm_shard $F --workload msm-shard && run quotient_fused $F --workload quotient \
+  && run quotient_generic $F --workload quotient --air generic && run verify $F --workload verify

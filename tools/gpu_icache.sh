@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 W=${1:?workload}; K=${2:?kernel regex}; N=${3:?name}
-B="python3 bench.py --workload $W --serial --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_EXTRA}"
+B="python3 bench.py --full --workload $W --serial --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_EXTRA}"
 pass() {  # pass-name counters...
   local n=$1; shift
   rm -rf gpurun_out/icache_${N}_$n

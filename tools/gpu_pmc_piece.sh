@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="python3 bench.py --serial --steps 1 --warmup 0 --no-cpu-baseline"
+B="python3 bench.py --full --serial --steps 1 --warmup 0 --no-cpu-baseline"
 R="--kernel-include-regex k_piece_sum29"
 pass() {  # name counters...
   local n=$1; shift

@@ -9,6 +9,7 @@ mkdir -p gpurun_out
 [ $# -ge 1 ] || { echo "usage: $0 <variant>..."; exit 2; }
 # PROBE_WORKLOADS (default "msm prove"): the bench.py workloads timed per library; PROBE_ARGS: extra
 # bench.py arguments for every run (e.g. "--air generic")
+PROBE_ARGS="--full $PROBE_ARGS"  # tools/gpu_ab.sh reads the per-kernel roofline of these lines
 run() {
   local line="$1"
   for w in ${PROBE_WORKLOADS:-msm prove}; do
