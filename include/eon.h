@@ -153,9 +153,11 @@ int eon_diag_clock_probe(eon_ctx* ctx, uint32_t launches, uint32_t iters, eon_cl
  * cases. */
 int eon_diag_prod_asm_check(eon_ctx* ctx, uint32_t n, uint32_t seed, uint32_t mismatches[3]);
 
-/* ABI version; bumped on any signature or struct-layout change (4: the verifier pairings and their
- * eon_g2_affine / eon_fq12 types; 3: eon_collective's all_to_all field).  Bindings must check it
- * at load time: a binding built against an older layout would pass a shorter eon_collective. */
+/* ABI version; bumped on any signature or struct-layout change (5: preprocessed columns in the
+ * generic quotient, eon_air_program_create_pp / eon_quotient_values_pp_dev, additive; 4: the
+ * verifier pairings and their eon_g2_affine / eon_fq12 types; 3: eon_collective's all_to_all
+ * field).  Bindings must check it at load time: a binding built against an older layout would pass
+ * a shorter eon_collective. */
 uint32_t eon_abi_version(void);
 
 /* ---- TwoAdicSubgroupDft<Fr> (dft/src/traits.rs:27-249) -----------------------------------
@@ -330,9 +332,11 @@ int eon_p2air_quotient_values_dev(eon_ctx* ctx, const eon_p2air* air, const eon_
  * root node of each constraint in assert order (the folder's constraint_index order,
  * folder.rs:81-85).  Leaves: EON_SYM_CONSTANT a = index into consts (canonical Fr);
  * EON_SYM_MAIN a = column, b = row offset (0 local, 1 next); EON_SYM_PUBLIC a = public index;
- * the three selectors (symbolic_builder.rs:205-221).  Preprocessed, permutation (LogUp) and
- * challenge variables are rejected (EON_E_ARG): the prove path has no preprocessed data and no
- * lookups (prover.rs:211-250 None branch). */
+ * the three selectors (symbolic_builder.rs:205-221); EON_SYM_PREPROCESSED a = column of the
+ * preprocessed trace (< the program's preprocessed width), b = row offset, a degree-1 leaf like
+ * EON_SYM_MAIN (symbolic_variable.rs:8-40; the folder's preprocessed window, folder.rs:25-40,
+ * prover.rs:677).  Permutation (LogUp) and challenge variables are rejected (EON_E_ARG): the prove
+ * path has no lookups (prover.rs:211-250 None branch). */
 enum {
     EON_SYM_CONSTANT = 0,
     EON_SYM_MAIN = 1,
@@ -367,7 +371,17 @@ typedef struct {
 int eon_air_program_create(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
                            uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints,
                            uint32_t width, uint32_t n_public, eon_air_program** out);
+/* The same for an AIR with `preprocessed_width` preprocessed columns (the preprocessed_width
+ * argument of get_symbolic_constraints, symbolic_builder.rs:72-80): EON_SYM_PREPROCESSED nodes may
+ * name columns below it.  eon_air_program_create is this call with preprocessed_width = 0, so it
+ * answers EON_E_ARG to every EON_SYM_PREPROCESSED node (column out of range). */
+int eon_air_program_create_pp(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
+                              uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints,
+                              uint32_t width, uint32_t preprocessed_width, uint32_t n_public,
+                              eon_air_program** out);
 void eon_air_program_destroy(eon_air_program* prog);
+/* the preprocessed width the program was compiled for (0 for eon_air_program_create) */
+uint32_t eon_air_program_preprocessed_width(const eon_air_program* prog);
 int eon_air_program_info(const eon_air_program* prog, eon_air_program_stats* out);
 /* get_log_quotient_degree (symbolic_builder.rs:15-43): log2_ceil(max(max_degree + is_zk, 2) - 1) */
 uint32_t eon_air_program_log_quotient_degree(const eon_air_program* prog, uint32_t is_zk);
@@ -379,6 +393,16 @@ uint32_t eon_air_program_log_quotient_degree(const eon_air_program* prog, uint32
 int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde, uint32_t log_n,
                             uint32_t log_qd, const eon_fr* alpha, const eon_fr* publics, uint32_t n_public,
                             eon_fr* out);
+/* The same with the preprocessed trace on the same quotient domain (prover.rs:321-322:
+ * get_evaluations_on_domain of the preprocessed data): `pre_lde` = 2^(log_n + log_qd) rows x
+ * preprocessed_width columns, row-major, natural order, device, read through the same row pair as
+ * `lde` (local = row i, next = row (i + 2^log_qd) mod Q; vertically_packed_row_pair,
+ * prover.rs:677, matrix/src/lib.rs:392-411).  pre_lde must be non-NULL exactly when the program's
+ * preprocessed width is > 0 (EON_E_ARG otherwise); eon_quotient_values_dev is this call with
+ * pre_lde = NULL and answers EON_E_ARG for a program with preprocessed columns. */
+int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde,
+                               const eon_fr* pre_lde, uint32_t log_n, uint32_t log_qd, const eon_fr* alpha,
+                               const eon_fr* publics, uint32_t n_public, eon_fr* out);
 
 /* out[i] = sum_{j<k} coeffs[j] * in[j * rows + i] (device in/out, host coeffs, 1 <= k <= 64):
  * the combine step of the lane-sharded quotient -- every rank all-gathers the

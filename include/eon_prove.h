@@ -13,6 +13,9 @@
  *                    (eon_prove_p2air_fs with an eon_challenger).
  *   eon_prove_air    the same for any AIR compiled into an eon_air_program (eon.h), with public
  *                    values (e.g. eon-uni-stark/tests/fib_air.rs's FibonacciAir)
+ *   eon_preprocessed PreprocessedProverData (eon-uni-stark/src/preprocessed.rs:12-24) from
+ *                    setup_preprocessed (:47-94), and eon_prove_air_pp, the Some(preprocessed)
+ *                    branch of prove_with_preprocessed (prover.rs:58-88, 190-208, 321-322, 431)
  *   eon_challenger   DuplexChallenger<Fr, Poseidon2Bn254<3>, 3, 2>
  *                    (challenger/src/duplex_challenger.rs, bn254/src/poseidon2.rs) on the host.
  * Conventions are eon.h's: 0 / negative EON_E_* codes (the reference panics), host outputs,
@@ -114,7 +117,7 @@ int eon_challenger_sample(eon_challenger* ch, eon_fr* out);
 int eon_challenger_state(const eon_challenger* ch, eon_fr out[3]);
 
 /* prove with the transcript of prove_with_preprocessed: observe log_ext_degree, log_degree, the
- * preprocessed width (0) and the trace commitment (prover.rs:196-202), sample alpha (:300),
+ * preprocessed width (0 here) and the trace commitment (prover.rs:196-202), sample alpha (:300),
  * observe the quotient commitment (:373), sample zeta (:416).  `challenger` is the config's
  * initialised challenger and is advanced as the reference's; alpha_out / zeta_out (host,
  * nullable) receive the sampled challenges.  Sharded: the trace commitments are all-gathered
@@ -135,6 +138,58 @@ int eon_prove_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
                      const eon_fr* publics, uint32_t n_public, eon_challenger* challenger, eon_proof* out,
                      eon_fr* alpha_out, eon_fr* zeta_out);
 
+/* ---- preprocessed columns (eon-uni-stark/src/preprocessed.rs) -------------------------------
+ * eon_preprocessed is PreprocessedProverData (preprocessed.rs:12-24): the width, degree_bits, the
+ * column commitments and the Pcs prover data (coefficients and their prepared MSM digits) of a
+ * preprocessed trace committed once per AIR / degree and reused by every prove.  The verifier's
+ * PreprocessedVerifierKey (:30-40) is (width, degree_bits, commitment): eon_preprocessed_info and
+ * eon_preprocessed_commitment.
+ *
+ * eon_setup_preprocessed is setup_preprocessed (:47-94): KzgPcs::commit of `pre_trace` (device,
+ * height x width, row-major) on natural_domain_for_degree(height) (:78-80).  The matrix is copied
+ * and need not outlive the call.  width == 0 is EON_E_SHAPE (the reference returns None, :68-70,
+ * and the caller proves without preprocessed data); height must be a power of two.  Destroy the
+ * handle before its pcs. */
+typedef struct eon_preprocessed eon_preprocessed;
+int eon_setup_preprocessed(eon_kzg_pcs* pcs, const eon_fr* pre_trace, uint64_t height, uint32_t width,
+                           eon_preprocessed** out);
+void eon_preprocessed_destroy(eon_preprocessed* pp);
+/* width and degree_bits (either pointer may be NULL) */
+int eon_preprocessed_info(const eon_preprocessed* pp, uint32_t* width, uint32_t* degree_bits);
+/* the column commitments, out[width] (host) */
+int eon_preprocessed_commitment(const eon_preprocessed* pp, eon_g1_affine* out);
+
+/* eon_proof plus the preprocessed openings (proof.rs opened_values.preprocessed_local / _next,
+ * prover.rs:463-493); Wp = the preprocessed width.  The commitment is the setup's own (the
+ * verifier takes it from its key, verifier.rs:165-235), copied here for convenience.  The three
+ * arrays are untouched (and may be NULL) when the prove ran without preprocessed data. */
+typedef struct {
+    eon_proof base;
+    eon_g1_affine* preprocessed_commit;    /* [Wp] */
+    eon_fr* preprocessed_opened;           /* [2][Wp]: values at zeta, zeta * h */
+    eon_g1_affine* preprocessed_witnesses; /* [2][Wp] */
+} eon_proof_pp;
+
+/* eon_prove_air / eon_prove_air_fs for a program with preprocessed columns
+ * (eon_air_program_create_pp), in the reference's order: commit the trace; observe log_ext_degree,
+ * log_degree, the preprocessed width Wp, the trace commitment, then the preprocessed commitment,
+ * then the public values (prover.rs:196-208); alpha; get_evaluations_on_domain of the trace and of
+ * the preprocessed data on the quotient domain (:315-322; the latter recomputed each prove, counted
+ * in EON_STAGE_TRACE_LDE); quotient_values, commit_quotient, zeta; open the trace at
+ * {zeta, zeta h}, the quotient chunks at {zeta}, the preprocessed data at {zeta, zeta h}
+ * (:426-439).  The reference's asserts (prover.rs:58-88): pp's degree_bits != log2(height) or pp's
+ * width != the program's preprocessed width is EON_E_SHAPE; a program with preprocessed columns
+ * and pp == NULL is EON_E_ARG ("no PreprocessedProverData was provided"; eon_prove_air[_fs] answer
+ * the same), as is a pp committed with another pcs.  A program without preprocessed columns and
+ * pp == NULL proves exactly as eon_prove_air.  No sharding. */
+int eon_prove_air_pp(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                     const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp, const eon_fr* alpha,
+                     const eon_fr* zeta, eon_proof_pp* out);
+int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                        const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp,
+                        eon_challenger* challenger, eon_proof_pp* out, eon_fr* alpha_out, eon_fr* zeta_out);
+
+/* bumped on any signature or struct-layout change (4: the preprocessed surface above, additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

@@ -148,16 +148,21 @@ class AirProgram:
     constraint DAG get_symbolic_constraints returns (symbolic.py) -> device program.
 
     ``air`` is any object with ``width()``, ``num_public_values()`` and ``eval(builder)`` on the
-    EonAirBuilder surface (symbolic.SymbolicAirBuilder)."""
+    EonAirBuilder surface (symbolic.SymbolicAirBuilder).  An AIR with preprocessed columns
+    (``builder.preprocessed()``) also has ``preprocessed_width()``, or the width is given here;
+    their LDE is then a second matrix of ``quotient_values``."""
 
-    def __init__(self, air, ctx: Context | None = None):
+    def __init__(self, air, ctx: Context | None = None, preprocessed_width: int | None = None):
         from . import symbolic
 
         self.ctx = ctx or default_context(0)
         self.air = air
         self.n_public = int(air.num_public_values())
         self.width = symbolic.air_width(air)
-        cs = symbolic.get_symbolic_constraints(air, 0, self.n_public)
+        if preprocessed_width is None:
+            preprocessed_width = air.preprocessed_width() if hasattr(air, "preprocessed_width") else 0
+        self.preprocessed_width = int(preprocessed_width)
+        cs = symbolic.get_symbolic_constraints(air, self.preprocessed_width, self.n_public)
         nodes, consts, roots = symbolic.serialize(cs)
         self.num_nodes = len(nodes)
         na = (_lib.eon_sym_node * max(1, len(nodes)))(*[_lib.eon_sym_node(*n) for n in nodes])
@@ -166,9 +171,10 @@ class AirProgram:
         ca = np.ascontiguousarray(ints_to_limbs(consts) if consts else np.zeros((1, 4), np.uint64))
         ra = np.ascontiguousarray(np.array(roots if roots else [0], dtype=np.uint32))
         h = ctypes.c_void_p()
-        self.ctx.check(self.ctx.lib.eon_air_program_create(
+        self.ctx.check(self.ctx.lib.eon_air_program_create_pp(
             self.ctx.handle, na, len(nodes), ca.ctypes.data_as(ctypes.c_void_p), len(consts),
-            ra.ctypes.data_as(ctypes.c_void_p), len(roots), self.width, self.n_public, ctypes.byref(h)))
+            ra.ctypes.data_as(ctypes.c_void_p), len(roots), self.width, self.preprocessed_width, self.n_public,
+            ctypes.byref(h)))
         self._h = h
         st = _lib.eon_air_program_stats()
         self.ctx.check(self.ctx.lib.eon_air_program_info(h, ctypes.byref(st)))
@@ -183,8 +189,9 @@ class AirProgram:
     def log_quotient_degree(self, is_zk: int = 0) -> int:
         return int(self.ctx.lib.eon_air_program_log_quotient_degree(self._h, is_zk))
 
-    def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=()):
-        """quotient_values (prover.rs:539-709) on the trace's LDE over GENERATOR * K (natural)."""
+    def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=(), preprocessed_lde=None):
+        """quotient_values (prover.rs:539-709) on the trace's LDE over GENERATOR * K (natural);
+        `preprocessed_lde`: the preprocessed trace on the same domain, (Q, preprocessed_width, 4)."""
         import torch
 
         from .field import fr_to_abi
@@ -194,8 +201,16 @@ class AirProgram:
         a = fr_to_abi(alpha)
         pub = _publics_limbs(publics)
         self.ctx.set_stream(torch.cuda.current_stream(lde.device).cuda_stream)
-        self.ctx.check(self.ctx.lib.eon_quotient_values_dev(
-            self.ctx.handle, self._h, _dp(lde.contiguous()), log_n, log_qd, ctypes.byref(a),
+        if preprocessed_lde is None:
+            self.ctx.check(self.ctx.lib.eon_quotient_values_dev(
+                self.ctx.handle, self._h, _dp(lde.contiguous()), log_n, log_qd, ctypes.byref(a),
+                pub.ctypes.data_as(ctypes.c_void_p), len(publics), _dp(out)))
+            return out
+        pre = preprocessed_lde.contiguous()
+        if pre.device != lde.device or tuple(pre.shape) != (q, self.preprocessed_width, 4):
+            raise ValueError(f"preprocessed_lde must be ({q}, {self.preprocessed_width}, 4) on {lde.device}")
+        self.ctx.check(self.ctx.lib.eon_quotient_values_pp_dev(
+            self.ctx.handle, self._h, _dp(lde.contiguous()), _dp(pre), log_n, log_qd, ctypes.byref(a),
             pub.ctypes.data_as(ctypes.c_void_p), len(publics), _dp(out)))
         return out
 

@@ -7,8 +7,12 @@
 // constraint in the folder's order (each constraint's not-yet-computed sub-DAG in post-order, then
 // its ASSERT), and register-allocated by liveness (a register is reused right after its last read).
 // Leaves are operand modes, not instructions: trace column of the local / next row, a constant
-// (program constants, then the public values), a selector.  degree_multiple follows
-// symbolic_expression.rs:171-190, get_log_quotient_degree symbolic_builder.rs:15-43.
+// (program constants, then the public values), a selector.  A preprocessed column
+// (Entry::Preprocessed, symbolic_variable.rs:8-15; the folder's second window, folder.rs:25-40) is
+// the same local / next mode with its index past the main width: index W + c reads column c of the
+// second matrix `pre_lde` (Wp columns, same quotient coset, same row pair, prover.rs:677).
+// degree_multiple follows symbolic_expression.rs:171-190, get_log_quotient_degree
+// symbolic_builder.rs:15-43.
 //
 // Device side (k_air_quotient): one thread per quotient-domain row i runs the program with its
 // row window (local = row i, next = row (i + 2^qd) mod Q, vertically_packed_row_pair,
@@ -134,9 +138,17 @@ struct MemRegs {
     }
 };
 
+// PRE: the program reads preprocessed columns.  Without them the kernel is the one-matrix kernel,
+// instruction for instruction (the second matrix's compare and select are compiled out: measured at
+// +1 % on the Poseidon2-AIR when left in)
+template <bool PRE>
 struct Window {
+    static constexpr bool has_pre = PRE;
     const Fr* local;
     const Fr* next;
+    const Fr* pre_local;  // the preprocessed matrix's row pair (PRE only)
+    const Fr* pre_next;
+    uint32_t width;       // main width W: a local / next index >= W is preprocessed column index - W
     const F29* table;  // program constants, then public values: x 2^261 (< 2p), converted on the host
     const Fr* sels;   // is_first_row | is_last_row | is_transition, q each (null if unused)
     uint64_t row, q;
@@ -179,8 +191,8 @@ __device__ __forceinline__ bool hot_set(Hot& h, uint32_t i, const F29& x) {
 // kernel body (four slots written out) is 61 KB instead of 103 (round 6; the instruction cache hit
 // 99.7 % before, and the time did not change: 11.69 vs 11.64 ms, profiles/r06/s7)
 
-template <class RF>
-__device__ __forceinline__ F29 fetch(uint32_t opnd, const RF& rf, const F29& prev, const Hot& hot, const Window& w) {
+template <class RF, class Win>
+__device__ __forceinline__ F29 fetch(uint32_t opnd, const RF& rf, const F29& prev, const Hot& hot, const Win& w) {
     const uint32_t i = opnd & IDX_MASK;
     const bool raw = (opnd & OPND_RAW) != 0;
     const uint32_t m = opnd >> 29;
@@ -191,9 +203,13 @@ __device__ __forceinline__ F29 fetch(uint32_t opnd, const RF& rf, const F29& pre
         if (hot_get(hot, i, x)) return x;
         return rf.get(i - AIR_VREGS);
     }
-    // local / next row cell or a selector: the address picked by the (uniform) mode, one load
-    const Fr* p = m == M_LOCAL ? w.local + i
-                  : m == M_NEXT ? w.next + i
+    // local / next row cell (of the main or the preprocessed matrix: the index is uniform, so
+    // which one is a scalar compare) or a selector: the address picked by the (uniform) mode, one
+    // load
+    const bool pre = Win::has_pre && i >= w.width;
+    const uint32_t col = pre ? i - w.width : i;
+    const Fr* p = m == M_LOCAL ? (pre ? w.pre_local : w.local) + col
+                  : m == M_NEXT ? (pre ? w.pre_next : w.next) + col
                                 : w.sels + (uint64_t)(m - M_FIRST) * w.q + w.row;
     return ld29(p, raw);
 }
@@ -210,8 +226,8 @@ struct CodeBlock {
 // The four slots of a block are unrolled, each with its own product per op kind.  One shared body
 // (the slot's words picked by scalar selects, one product for MUL and ASSERT) measured slower,
 // 15.8 vs 14.8 ms for the Poseidon2-AIR at 2^18 rows (round 4, profiles/r04/s7): not kept.
-template <class RF>
-__device__ __forceinline__ void exec1(const Instr& in, RF& rf, const Window& w, const F29& alpha,
+template <class RF, class Win>
+__device__ __forceinline__ void exec1(const Instr& in, RF& rf, const Win& w, const F29& alpha,
                                       const F29& alpha2, F29& acc, F29& pend, F29& prev, Hot& hot) {
     const uint32_t opc = in.op & OP_MASK;
     if (opc == OP_NOP) return;
@@ -250,9 +266,9 @@ __device__ __forceinline__ void exec1(const Instr& in, RF& rf, const Window& w, 
     rf.set(in.dst - AIR_VREGS, r);
 }
 
-template <class RF>
+template <class RF, class Win>
 __device__ __forceinline__ void run_program(const CodeBlock* __restrict__ code, uint32_t n_blocks, RF& rf,
-                                            const Window& w, const F29& alpha, F29& acc) {
+                                            const Win& w, const F29& alpha, F29& acc) {
     if (n_blocks == 0) return;
     const F29 alpha2 = uniform29(sqr29<FrP>(alpha));
     F29 prev, pend;
@@ -282,10 +298,12 @@ __device__ __forceinline__ void run_program(const CodeBlock* __restrict__ code, 
     }
 }
 
-// MODE 0: registers in LDS; 1: in the global buffer `gregs` (n_regs 36-byte registers per row)
-template <int MODE>
+// MODE 0: registers in LDS; 1: in the global buffer `gregs` (n_regs 36-byte registers per row).
+// PRE: with the preprocessed matrix `pre_lde` (pre_width columns); otherwise both are unused.
+template <int MODE, bool PRE>
 __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __restrict__ code, uint32_t n_blocks,
                                                       uint32_t n_regs, const Fr* __restrict__ lde, uint32_t width,
+                                                      const Fr* __restrict__ pre_lde, uint32_t pre_width,
                                                       uint64_t q, uint64_t next_step, const F29* __restrict__ table,
                                                       const Fr* __restrict__ sels, const Fr* __restrict__ inv_van,
                                                       uint32_t nr_mask, Fr alpha, Fr* __restrict__ out,
@@ -293,7 +311,16 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
     extern __shared__ uint4 lds_regs[];
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= q) return;
-    Window w{lde + row * width, lde + ((row + next_step) & (q - 1)) * width, table, sels, row, q};
+    const uint64_t next_row = (row + next_step) & (q - 1);
+    Window<PRE> w{lde + row * width,
+                  lde + next_row * width,
+                  PRE ? pre_lde + row * pre_width : nullptr,
+                  PRE ? pre_lde + next_row * pre_width : nullptr,
+                  width,
+                  table,
+                  sels,
+                  row,
+                  q};
     F29 acc;
 #pragma unroll
     for (int i = 0; i < 9; i++) acc.l[i] = 0;
@@ -319,7 +346,7 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
 
 struct eon_air_program {
     eon_ctx* ctx = nullptr;
-    uint32_t width = 0, n_public = 0, n_constraints = 0, max_degree = 0, n_regs = 0, n_consts = 0;
+    uint32_t width = 0, pre_width = 0, n_public = 0, n_constraints = 0, max_degree = 0, n_regs = 0, n_consts = 0;
     bool uses_sels = false;
     std::vector<Instr> code;
     std::vector<Fr> consts;
@@ -344,8 +371,10 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
                uint32_t n_consts, const uint32_t* roots, uint32_t n_roots) {
     // operand indices are 28 bits (bit 28 is OPND_RAW): a wider main-column index, constant slot
     // or public slot would set the raw flag and read the wrong leaf
-    if (p->width > IDX_MASK || (uint64_t)n_consts + p->n_public > IDX_MASK)
-        return Status::err(EON_E_SHAPE, "trace width and constant + public slots must each be < 2^28");
+    // (the preprocessed columns share the local / next index space, after the main ones)
+    if ((uint64_t)p->width + p->pre_width > IDX_MASK || (uint64_t)n_consts + p->n_public > IDX_MASK)
+        return Status::err(EON_E_SHAPE, "trace width (main + preprocessed) and constant + public slots must each "
+                                        "be < 2^28");
     // value numbering
     std::vector<uint32_t> vn(n_nodes);
     std::vector<uint32_t> degree(n_nodes);
@@ -432,11 +461,18 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
                 vn[i] = intern(OP_NEG, vn[nd.a], 0);
                 degree[i] = degree[nd.a];
                 break;
-            case EON_SYM_PREPROCESSED:
+            case EON_SYM_PREPROCESSED:  // a trace leaf of the second matrix: index W + column
+                if (nd.a >= p->pre_width || nd.b > 1)
+                    return Status::err(EON_E_ARG, "preprocessed variable out of range (column " + std::to_string(nd.a) +
+                                                      ", offset " + std::to_string(nd.b) + ", preprocessed width " +
+                                                      std::to_string(p->pre_width) + ")");
+                vn[i] = intern(LEAF, (nd.b ? M_NEXT : M_LOCAL) << 29 | (p->width + nd.a), 0);
+                degree[i] = 1;
+                break;
             case EON_SYM_PERMUTATION:
             case EON_SYM_CHALLENGE:
-                return Status::err(EON_E_ARG, "preprocessed / permutation (LogUp) / challenge variables are not "
-                                              "supported by the generic quotient program");
+                return Status::err(EON_E_ARG, "permutation (LogUp) / challenge variables are not supported by the "
+                                              "generic quotient program");
             default:
                 return Status::err(EON_E_ARG, "unknown node kind " + std::to_string(nd.kind));
         }
@@ -624,9 +660,9 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
 
 extern "C" {
 
-int eon_air_program_create(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
-                           uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints, uint32_t width,
-                           uint32_t n_public, eon_air_program** out) {
+int eon_air_program_create_pp(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
+                              uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints, uint32_t width,
+                              uint32_t preprocessed_width, uint32_t n_public, eon_air_program** out) {
     if (!ctx) return EON_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
@@ -636,6 +672,7 @@ int eon_air_program_create(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_n
         auto* p = new eon_air_program();
         p->ctx = ctx;
         p->width = width;
+        p->pre_width = preprocessed_width;
         p->n_public = n_public;
         p->n_constraints = n_constraints;
         Status c = compile(p, nodes, n_nodes, consts, n_consts, constraints, n_constraints);
@@ -662,6 +699,13 @@ int eon_air_program_create(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_n
     return finish(ctx, s);
 }
 
+int eon_air_program_create(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
+                           uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints, uint32_t width,
+                           uint32_t n_public, eon_air_program** out) {
+    return eon_air_program_create_pp(ctx, nodes, n_nodes, consts, n_consts, constraints, n_constraints, width, 0,
+                                     n_public, out);
+}
+
 void eon_air_program_destroy(eon_air_program* p) {
     if (!p) return;
     std::lock_guard<std::mutex> lk(p->ctx->mu);
@@ -683,6 +727,8 @@ int eon_air_program_info(const eon_air_program* p, eon_air_program_stats* out) {
     return EON_OK;
 }
 
+uint32_t eon_air_program_preprocessed_width(const eon_air_program* p) { return p ? p->pre_width : 0; }
+
 uint32_t eon_air_program_log_quotient_degree(const eon_air_program* p, uint32_t is_zk) {
     // symbolic_builder.rs:28-42: log2_ceil(max(max_degree + is_zk, 2) - 1)
     if (!p) return 0;
@@ -692,9 +738,9 @@ uint32_t eon_air_program_log_quotient_degree(const eon_air_program* p, uint32_t 
     return b;
 }
 
-int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* lde, uint32_t log_n,
-                            uint32_t log_qd, const eon_fr* alpha, const eon_fr* publics, uint32_t n_public,
-                            eon_fr* out) {
+int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* lde, const eon_fr* pre_lde,
+                               uint32_t log_n, uint32_t log_qd, const eon_fr* alpha, const eon_fr* publics,
+                               uint32_t n_public, eon_fr* out) {
     if (!ctx || !prog_c) return EON_E_ARG;
     auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -702,6 +748,10 @@ int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog_c, const e
     Status s = [&]() -> Status {
         if (!lde || !alpha || !out || (n_public && !publics)) return Status::err(EON_E_ARG, "null argument");
         if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+        if ((pre_lde != nullptr) != (prog->pre_width > 0))
+            return Status::err(EON_E_ARG, prog->pre_width > 0
+                                              ? "the program reads preprocessed columns: pre_lde must not be null"
+                                              : "the program has no preprocessed columns: pre_lde must be null");
         if (n_public != prog->n_public)
             return Status::err(EON_E_SHAPE, "public value count differs from the program's");
         const uint32_t log_q = log_n + log_qd;
@@ -760,27 +810,43 @@ int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog_c, const e
             const uint32_t opc = in.op & OP_MASK;
             products += (opc == OP_MUL || opc == OP_SQR || opc == OP_ASSERT) ? 1 : 0;
         }
-        ctx->prof.begin("k_air_quotient", q * (uint64_t)prog->width * 32 + q * 32, ctx->stream, q * products);
+        ctx->prof.begin("k_air_quotient", q * ((uint64_t)prog->width + prog->pre_width) * 32 + q * 32, ctx->stream,
+                        q * products);
         const CodeBlock* code = prog->d_code.as<CodeBlock>();
         const uint32_t n_blocks = (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK);
         const Fr* lde_f = reinterpret_cast<const Fr*>(lde);
         const Fr* sel = prog->uses_sels ? prog->d_sels.as<Fr>() : nullptr;
         Fr* out_f = reinterpret_cast<Fr*>(out);
-        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, uint64_t, uint64_t,
-                                  const F29*, const Fr*, const Fr*, uint32_t, Fr, Fr*, uint4*);
-        const KernelFn kern = mode == 0 ? k_air_quotient<0> : k_air_quotient<1>;
+        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
+                                  uint64_t, uint64_t, const F29*, const Fr*, const Fr*, uint32_t, Fr, Fr*, uint4*);
+        const bool has_pre = prog->pre_width > 0;
+        const KernelFn kern = mode == 0 ? (has_pre ? k_air_quotient<0, true> : k_air_quotient<0, false>)
+                                        : (has_pre ? k_air_quotient<1, true> : k_air_quotient<1, false>);
         if (mode == 0)  // per launch: the attribute is per device, and this context's device may
                         // differ from the one another context set it on
             EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, ctx->stream, code, n_blocks, prog->n_regs, lde_f,
-                           prog->width, q, 1ull << log_qd, prog->d_table.as<F29>(), sel, inv_van, nr_mask, al, out_f,
+                           prog->width, reinterpret_cast<const Fr*>(pre_lde), prog->pre_width, q, 1ull << log_qd,
+                           prog->d_table.as<F29>(), sel, inv_van, nr_mask, al, out_f,
                            mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
         ctx->prof.end(ctx->stream);
         EON_HIP(hipGetLastError());
         return Status::ok();
     }();
     return finish(ctx, s);
+}
+
+int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde, uint32_t log_n,
+                            uint32_t log_qd, const eon_fr* alpha, const eon_fr* publics, uint32_t n_public,
+                            eon_fr* out) {
+    if (!ctx || !prog) return EON_E_ARG;
+    if (prog->pre_width > 0) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        return finish(ctx, Status::err(EON_E_ARG, "the program reads preprocessed columns: call "
+                                                  "eon_quotient_values_pp_dev with their LDE"));
+    }
+    return eon_quotient_values_pp_dev(ctx, prog, lde, nullptr, log_n, log_qd, alpha, publics, n_public, out);
 }
 
 }  // extern "C"

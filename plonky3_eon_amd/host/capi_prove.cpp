@@ -1,5 +1,6 @@
 // extern "C" surface of the prove driver (include/eon_prove.h).
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "eon_prove.h"
@@ -9,6 +10,10 @@
 struct eon_kzg_pcs {
     eon_host::KzgPcs* pcs = nullptr;
     std::string last_error;
+};
+
+struct eon_preprocessed {
+    std::unique_ptr<eon_host::Preprocessed> pp;
 };
 
 struct eon_challenger {
@@ -36,12 +41,18 @@ int guarded(eon_kzg_pcs* h, F&& f) {
 }
 
 void copy_out(const eon_host::Proof& p, eon_proof* out);
+void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out);
+
+bool proof_arrays_ok(const eon_proof* out) {
+    return out->trace_commit && out->quotient_commit && out->trace_opened && out->trace_witnesses &&
+           out->quotient_opened && out->quotient_witnesses;
+}
 
 }  // namespace
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 3; }
+uint32_t eon_prove_abi_version(void) { return 4; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -179,6 +190,79 @@ int eon_prove_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
     });
 }
 
+int eon_setup_preprocessed(eon_kzg_pcs* pcs, const eon_fr* pre_trace, uint64_t height, uint32_t width,
+                           eon_preprocessed** out) {
+    if (!pcs || !pcs->pcs) return EON_E_ARG;
+    return guarded(pcs, [&] {
+        using namespace eon_host;
+        if (!out) throw Error(EON_E_ARG, "null argument");
+        auto* h = new eon_preprocessed();
+        try {
+            h->pp = setup_preprocessed(*pcs->pcs, pre_trace, height, width);
+        } catch (...) {
+            delete h;
+            throw;
+        }
+        *out = h;
+    });
+}
+
+void eon_preprocessed_destroy(eon_preprocessed* pp) { delete pp; }
+
+int eon_preprocessed_info(const eon_preprocessed* pp, uint32_t* width, uint32_t* degree_bits) {
+    if (!pp || !pp->pp) return EON_E_ARG;
+    if (width) *width = pp->pp->width;
+    if (degree_bits) *degree_bits = pp->pp->degree_bits;
+    return EON_OK;
+}
+
+int eon_preprocessed_commitment(const eon_preprocessed* pp, eon_g1_affine* out) {
+    if (!pp || !pp->pp || !out) return EON_E_ARG;
+    std::memcpy(out, pp->pp->commitment.data(), pp->pp->commitment.size() * sizeof(eon_g1_affine));
+    return EON_OK;
+}
+
+int eon_prove_air_pp(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                     const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp, const eon_fr* alpha,
+                     const eon_fr* zeta, eon_proof_pp* out) {
+    if (!pcs || !pcs->pcs || !prog || !trace || !alpha || !zeta || !out || (n_public && !publics))
+        return EON_E_ARG;
+    if (!proof_arrays_ok(&out->base)) return EON_E_ARG;
+    return guarded(pcs, [&] {
+        using namespace eon_host;
+        if (pp && (!out->preprocessed_commit || !out->preprocessed_opened || !out->preprocessed_witnesses))
+            throw Error(EON_E_ARG, "null preprocessed output arrays");
+        AirRef a;
+        a.prog = prog;
+        a.publics = publics;
+        a.n_public = n_public;
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
+                        pp ? pp->pp.get() : nullptr);
+        copy_out_pp(p, out);
+    });
+}
+
+int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                        const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp,
+                        eon_challenger* challenger, eon_proof_pp* out, eon_fr* alpha_out, eon_fr* zeta_out) {
+    if (!pcs || !pcs->pcs || !prog || !trace || !challenger || !out || (n_public && !publics)) return EON_E_ARG;
+    if (!proof_arrays_ok(&out->base)) return EON_E_ARG;
+    return guarded(pcs, [&] {
+        using namespace eon_host;
+        if (pp && (!out->preprocessed_commit || !out->preprocessed_opened || !out->preprocessed_witnesses))
+            throw Error(EON_E_ARG, "null preprocessed output arrays");
+        AirRef a;
+        a.prog = prog;
+        a.publics = publics;
+        a.n_public = n_public;
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch,
+                        pp ? pp->pp.get() : nullptr);
+        copy_out_pp(p, out);
+        if (alpha_out) *alpha_out = p.alpha.abi();
+        if (zeta_out) *zeta_out = p.zeta.abi();
+    });
+}
+
 int eon_prove_p2air_fs(eon_kzg_pcs* pcs, const eon_p2air* air, const eon_fr* trace, uint64_t height,
                        eon_challenger* challenger, uint32_t max_constraint_degree,
                        const eon_collective* shard, eon_proof* out, eon_fr* alpha_out, eon_fr* zeta_out) {
@@ -214,6 +298,17 @@ void copy_out(const eon_host::Proof& p, eon_proof* out) {
     std::memcpy(out->quotient_witnesses, p.quotient_witnesses.data(), c * sizeof(eon_g1_affine));
     out->degree_bits = p.degree_bits;
     for (int s = 0; s < EON_STAGES; s++) out->stage_ms[s] = p.stage_ms[s];
+}
+
+void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out) {
+    copy_out(p, &out->base);
+    const size_t w = p.pre_commit.size();
+    if (!w) return;
+    std::memcpy(out->preprocessed_commit, p.pre_commit.data(), w * sizeof(eon_g1_affine));
+    for (int k = 0; k < 2; k++) {
+        std::memcpy(out->preprocessed_opened + k * w, p.pre_opened[k].data(), w * sizeof(eon_fr));
+        std::memcpy(out->preprocessed_witnesses + k * w, p.pre_witnesses[k].data(), w * sizeof(eon_g1_affine));
+    }
 }
 
 }  // namespace

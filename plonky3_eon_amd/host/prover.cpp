@@ -1,7 +1,9 @@
 // See prover.h.  Stage order and span names follow prove_with_preprocessed
 // (eon-uni-stark/src/prover.rs): commit (186-187) -> quotient domain (307-308) -> LDE (315) ->
 // quotient_values (328-342) -> commit_quotient (371-372) -> open at [zeta, zeta h] and [zeta] per
-// chunk (416-442).
+// chunk (416-442).  With preprocessed columns (setup_preprocessed, preprocessed.rs:47-94) their
+// commitment is observed after the trace's (203-205), their evaluations on the quotient domain are
+// read by the constraints (321-322) and they are opened last, at [zeta, zeta h] (431).
 //
 // Lane sharding: the vectorized AIR evaluates its lanes one after another
 // (poseidon2-air/src/vectorized.rs:259-274), so lane v owns columns [164 v, 164 v + 164) and
@@ -52,9 +54,35 @@ uint32_t AirRef::width() const {
     return 0;
 }
 
+std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_trace, uint64_t height,
+                                                 uint32_t width) {
+    eon_ctx* ctx = pcs.ctx();
+    if (width == 0)  // preprocessed.rs:68-70 returns None: the caller proves without one
+        throw Error(EON_E_SHAPE, "the preprocessed trace has no columns: prove without preprocessed data");
+    if (!pre_trace) throw Error(EON_E_ARG, "null preprocessed trace");
+    if (height == 0 || (height & (height - 1)))
+        throw Error(EON_E_SHAPE, "preprocessed trace height must be a power of two");
+    auto pp = std::make_unique<Preprocessed>();
+    pp->pcs = &pcs;
+    pp->width = width;
+    pp->degree_bits = 63 - __builtin_clzll(height);
+    // the handle owns its evaluations (the reference's ProverData keeps them, kzg/src/pcs.rs:46-63)
+    DeviceMatrix evals = DeviceMatrix::alloc(height, width);
+    hipStream_t st = static_cast<hipStream_t>(eon_ctx_stream(ctx));
+    hip_ok(hipMemcpyAsync(evals.mutable_data(), pre_trace, height * width * sizeof(eon_fr), hipMemcpyDeviceToDevice,
+                          st),
+           "preprocessed trace");
+    std::vector<std::pair<Domain, DeviceMatrix>> ev;
+    ev.emplace_back(pcs.natural_domain_for_degree(height), std::move(evals));
+    std::vector<std::vector<eon_g1_affine>> commit;
+    pcs.commit(std::move(ev), commit, pp->data);  // preprocessed.rs:79-80
+    pp->commitment = std::move(commit[0]);
+    return pp;
+}
+
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha_in,
             const Fr& zeta_in, uint32_t max_constraint_degree, const eon_collective* shard,
-            DuplexChallenger* challenger) {
+            DuplexChallenger* challenger, const Preprocessed* pp) {
     eon_ctx* ctx = pcs.ctx();
     using clock = std::chrono::steady_clock;
     auto tick = [&] {
@@ -78,6 +106,21 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     const uint32_t world = shard ? shard->world : 1, rank = shard ? shard->rank : 0;
     const uint32_t vector_len = local_vl * world;
     const uint32_t log_n = 63 - __builtin_clzll(height);
+    // the preprocessed data against the AIR's declaration (prover.rs:58-88: the reference panics)
+    const uint32_t pre_width = air.prog ? eon_air_program_preprocessed_width(air.prog) : 0;
+    if (pre_width > 0 && !pp)
+        throw Error(EON_E_ARG, "the program has preprocessed columns but no preprocessed data was provided "
+                               "(eon_setup_preprocessed, eon_prove_air_pp)");
+    if (pp) {
+        if (shard) throw Error(EON_E_ARG, "preprocessed columns are not lane-sharded");
+        if (pp->pcs != &pcs) throw Error(EON_E_ARG, "the preprocessed data was committed with another pcs");
+        if (pp->degree_bits != log_n)
+            throw Error(EON_E_SHAPE, "preprocessed degree_bits " + std::to_string(pp->degree_bits) +
+                                         " differs from the trace's " + std::to_string(log_n));
+        if (pp->width != pre_width)
+            throw Error(EON_E_SHAPE, "preprocessed width " + std::to_string(pp->width) +
+                                         " differs from the AIR's " + std::to_string(pre_width));
+    }
     // get_log_quotient_degree (prover.rs:150-157): the program's own constraint degrees
     const uint32_t log_qd =
         air.prog ? eon_air_program_log_quotient_degree(air.prog, 0) : log_quotient_degree(max_constraint_degree);
@@ -93,7 +136,7 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     std::vector<MatrixProverData> trace_data;
     const Domain quotient_domain = trace_domain.create_disjoint_domain(1ull << (log_n + log_qd));
     const uint64_t q_rows = quotient_domain.size();
-    DeviceMatrix lde;
+    DeviceMatrix lde, pre_lde;
     clock::time_point t1, t2;
     {
         std::vector<std::pair<Domain, DeviceMatrix>> ev;
@@ -123,8 +166,9 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         fs_thread = std::thread([&] {
             challenger->observe(fr_from_u64(log_n));  // log_ext_degree (ZK off)
             challenger->observe(fr_from_u64(log_n));  // log_degree
-            challenger->observe(fr_from_u64(0));      // preprocessed width
+            challenger->observe(fr_from_u64(pre_width));  // preprocessed width
             challenger->observe_g1(full_commit.data(), full_commit.size());
+            if (pp) challenger->observe_g1(pp->commitment.data(), pp->commitment.size());  // prover.rs:203-205
             for (uint32_t i = 0; i < air.n_public; i++)  // observe_slice(public_values), prover.rs:208
                 challenger->observe(Fr::from_abi(air.publics[i]));
             alpha = challenger->sample();  // no lookups
@@ -133,6 +177,8 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     // the trace LDE (prover.rs:315) while the host thread runs the transcript up to alpha
     try {
         lde = pcs.get_evaluations_on_domain(trace_data, 0, quotient_domain);
+        // recomputed each prove, as the reference does (prover.rs:321-322)
+        if (pp) pre_lde = pcs.get_evaluations_on_domain(pp->data, 0, quotient_domain);
     } catch (...) {
         if (fs_thread.joinable()) fs_thread.join();
         throw;
@@ -145,6 +191,11 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         if (air.p2)
             check(ctx, eon_p2air_quotient_values_dev(ctx, air.p2, lde.data(), log_n, log_qd, &a, qv.mutable_data()),
                   "quotient_values");
+        else if (pp)
+            check(ctx,
+                  eon_quotient_values_pp_dev(ctx, air.prog, lde.data(), pre_lde.data(), log_n, log_qd, &a,
+                                             air.publics, air.n_public, qv.mutable_data()),
+                  "quotient_values");
         else
             check(ctx,
                   eon_quotient_values_dev(ctx, air.prog, lde.data(), log_n, log_qd, &a, air.publics, air.n_public,
@@ -153,6 +204,7 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     }
     check(ctx, eon_ctx_synchronize(ctx), "quotient_values");
     lde = DeviceMatrix();  // back to the buffer cache before the opening
+    pre_lde = DeviceMatrix();
     auto t3 = tick();
     if (shard) {
         DeviceBuffer parts(sizeof(eon_fr) * q_rows * world);
@@ -203,6 +255,11 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     rounds[0].points = {{zeta, zeta_next}};
     rounds[1].data = &quotient_data;
     rounds[1].points.assign(quotient_data.size(), std::vector<Fr>{zeta});
+    if (pp) {  // round3 (prover.rs:431): after the quotient chunks
+        rounds.emplace_back();
+        rounds[2].data = &pp->data;
+        rounds[2].points = {{zeta, zeta_next}};
+    }
     // the opening bases are the same on every rank: sharded over the process group
     // (eon_ctx_set_collective)
     struct CollectiveScope {
@@ -246,6 +303,13 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
             const uint64_t* r = &all[((uint64_t)(c % world) * chunk_slots + c / world) * QREC];
             std::memcpy(&proof.quotient_opened[c], r, 32);
             std::memcpy(&proof.quotient_witnesses[c], r + 4, 64);
+        }
+    }
+    if (pp) {
+        proof.pre_commit = pp->commitment;
+        for (int p = 0; p < 2; p++) {
+            proof.pre_opened[p] = opened[2].values[0][p];
+            proof.pre_witnesses[p] = opened[2].witnesses[0][p];
         }
     }
     const Opened& tr = opened[0];

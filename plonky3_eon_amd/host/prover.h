@@ -1,7 +1,8 @@
 // prove_with_preprocessed (eon-uni-stark/src/prover.rs:28-512) over KzgPcs, as a C++ driver above
 // eon.h, for the Poseidon2-AIR (fused quotient kernel) or any AIR given as a constraint program
-// with public values: no preprocessed columns, no lookups, ZK off (KzgPcs::ZK = false,
-// kzg/src/pcs.rs:216), Challenge = Fr; alpha and zeta are inputs or sampled from a
+// with public values and, optionally, preprocessed columns (the Some(preprocessed) branch:
+// setup_preprocessed, eon-uni-stark/src/preprocessed.rs:47-94): no lookups, ZK off (KzgPcs::ZK =
+// false, kzg/src/pcs.rs:216), Challenge = Fr; alpha and zeta are inputs or sampled from a
 // DuplexChallenger.
 #pragma once
 #include "eon_prove.h"
@@ -23,7 +24,26 @@ struct Proof {
     uint32_t degree_bits = 0;
     double stage_ms[EON_STAGES] = {};
     Fr alpha, zeta;  // the challenges used
+    // with preprocessed columns (proof.rs opened_values.preprocessed_local / _next; the commitment
+    // is the setup's, carried for the caller's convenience)
+    std::vector<eon_g1_affine> pre_commit;        // [Wp]
+    std::vector<eon_fr> pre_opened[2];            // at zeta, zeta * h: [Wp] each
+    std::vector<eon_g1_affine> pre_witnesses[2];  // [Wp] each
 };
+
+// PreprocessedProverData (preprocessed.rs:12-24): the preprocessed trace committed once per
+// AIR / degree (KzgPcs::commit on the natural domain) and reused by every prove.
+struct Preprocessed {
+    const KzgPcs* pcs = nullptr;  // the pcs it was committed with
+    uint32_t width = 0, degree_bits = 0;
+    std::vector<eon_g1_affine> commitment;  // [width]
+    std::vector<MatrixProverData> data;     // one matrix: evaluations, coefficients, prepared digits
+};
+
+// setup_preprocessed (preprocessed.rs:47-94): `pre_trace` is height x width on device and is
+// copied (it need not outlive the call).  width == 0 is EON_E_SHAPE (the reference returns None).
+std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_trace, uint64_t height,
+                                                 uint32_t width);
 
 // The AIR being proved: the fused Poseidon2-AIR kernel (lane-shardable), or a generic constraint
 // program compiled from get_symbolic_constraints (eon_air_program) with its public values.
@@ -38,9 +58,12 @@ struct AirRef {
 // `trace`: this rank's height x width(air) device trace.  With `shard` (world > 1, Poseidon2 only)
 // the AIR is the rank's lane range; every rank returns the full proof.  With `challenger`, alpha
 // and zeta are sampled from it (prover.rs:196-208, 300, 373, 416) and the inputs are ignored.
-// max_constraint_degree is the Poseidon2-AIR's (3); a program carries its own.
+// max_constraint_degree is the Poseidon2-AIR's (3); a program carries its own.  `preprocessed`
+// (programs only, no sharding) is required exactly when the program has preprocessed columns: it is
+// observed after the trace commitment (prover.rs:196-208), extended to the quotient domain for the
+// constraints (:321-322) and opened at {zeta, zeta h} in a third round (:426-439).
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha,
             const Fr& zeta, uint32_t max_constraint_degree, const eon_collective* shard,
-            DuplexChallenger* challenger = nullptr);
+            DuplexChallenger* challenger = nullptr, const Preprocessed* preprocessed = nullptr);
 
 }  // namespace eon_host

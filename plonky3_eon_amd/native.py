@@ -42,6 +42,11 @@ class eon_proof(ctypes.Structure):
                 ("stage_ms", ctypes.c_double * EON_STAGES)]
 
 
+class eon_proof_pp(ctypes.Structure):
+    _fields_ = [("base", eon_proof), ("preprocessed_commit", _P), ("preprocessed_opened", _P),
+                ("preprocessed_witnesses", _P)]
+
+
 # name -> (restype, argtypes): every entry point of include/eon_prove.h
 SIGNATURES = {
     "eon_prove_abi_version": (_U32, []),
@@ -69,6 +74,12 @@ SIGNATURES = {
                                   ctypes.POINTER(eon_proof), _P, _P]),
     "eon_prove_air": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_proof)]),
     "eon_prove_air_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, ctypes.POINTER(eon_proof), _P, _P]),
+    "eon_setup_preprocessed": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(_P)]),
+    "eon_preprocessed_destroy": (None, [_P]),
+    "eon_preprocessed_info": (_INT, [_P, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "eon_preprocessed_commitment": (_INT, [_P, _P]),
+    "eon_prove_air_pp": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, ctypes.POINTER(eon_proof_pp)]),
+    "eon_prove_air_pp_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_pp), _P, _P]),
 }
 
 _plib = None
@@ -285,15 +296,60 @@ class Challenger:
             pass
 
 
+class Preprocessed:
+    """eon_preprocessed: PreprocessedProverData (eon-uni-stark/src/preprocessed.rs:12-24), the
+    preprocessed trace committed once and reused by every prove; (width, degree_bits, commitment)
+    is the verifier's PreprocessedVerifierKey."""
+
+    def __init__(self, pcs: NativeKzgPcs, handle):
+        self.pcs = pcs  # the handle's data lives on the pcs's context
+        self._h = handle
+        w, d = _U32(), _U32()
+        _check(pcs.lib.eon_preprocessed_info(handle, ctypes.byref(w), ctypes.byref(d)), "eon_preprocessed_info")
+        self.width, self.degree_bits = int(w.value), int(d.value)
+        self.commitment = np.zeros((self.width, 8), np.uint64)
+        _check(pcs.lib.eon_preprocessed_commitment(handle, _p(self.commitment)), "eon_preprocessed_commitment")
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.pcs.lib.eon_preprocessed_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def setup_preprocessed(pcs: NativeKzgPcs, pre_trace) -> Preprocessed:
+    """setup_preprocessed (preprocessed.rs:47-94): commit the (N, Wp, 4) device tensor `pre_trace`
+    on the natural domain of N.  The tensor is copied; it need not outlive the call."""
+    import torch
+
+    t = pre_trace.contiguous()
+    torch.cuda.synchronize(t.device)  # produced on torch's stream
+    pcs.ctx.set_stream(None)
+    h = _P()
+    pcs.check(pcs.lib.eon_setup_preprocessed(pcs._h, ctypes.c_void_p(t.data_ptr()), int(t.shape[0]), int(t.shape[1]),
+                                             ctypes.byref(h)))
+    return Preprocessed(pcs, h)
+
+
 def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | None,
                  max_constraint_degree: int = 3, collective=None, challenger: Challenger | None = None,
-                 public_values=()) -> Proof:
+                 public_values=(), preprocessed: Preprocessed | None = None) -> Proof:
     """prover.prove through the C++ driver.  `air` is a Poseidon2Air (fused quotient kernel) or an
     air.AirProgram (any AIR, with `public_values`: canonical ints).  `trace`: (N, width, 4) device
     tensor; with a collective (world > 1, Poseidon2 only) `air`/`trace` are this rank's lanes and
     the proof is the full one.  With `challenger` (eon_prove_*_fs) alpha and zeta are sampled from
     the transcript and returned in proof.alpha / proof.zeta (canonical ints); the arguments are
-    ignored."""
+    ignored.  With `preprocessed` (setup_preprocessed; generic AIRs only) the proof carries its
+    commitment and a third Opened entry, the preprocessed columns at zeta and zeta * h."""
     from .air import AirProgram, _publics_limbs
 
     generic = isinstance(air, AirProgram)
@@ -308,6 +364,15 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     qo = np.zeros((chunks, 4), np.uint64)
     qw = np.zeros((chunks, 8), np.uint64)
     out = eon_proof(_p(tc), _p(qc), _p(to), _p(tw), _p(qo), _p(qw), 0)
+    if preprocessed is not None:
+        if not generic or collective is not None:
+            raise ValueError("preprocessed columns need an AirProgram and no collective")
+        wp = preprocessed.width
+        pc = np.zeros((wp, 8), np.uint64)
+        po = np.zeros((2, wp, 4), np.uint64)
+        pw = np.zeros((2, wp, 8), np.uint64)
+        out_pp = eon_proof_pp(out, _p(pc), _p(po), _p(pw))
+        out = out_pp.base  # a view: the driver's degree_bits and stage_ms land here
     t = trace.contiguous()
     import torch
 
@@ -321,7 +386,11 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     tp = ctypes.c_void_p(t.data_ptr())
     if challenger is None:
         a, z = fr_to_abi(alpha), fr_to_abi(zeta)
-        if generic:
+        if preprocessed is not None:
+            pcs.check(pcs.lib.eon_prove_air_pp(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                               preprocessed.handle, ctypes.byref(a), ctypes.byref(z),
+                                               ctypes.byref(out_pp)))
+        elif generic:
             pcs.check(pcs.lib.eon_prove_air(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, ctypes.byref(a),
                                             ctypes.byref(z), ctypes.byref(out)))
         else:
@@ -329,7 +398,11 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
                                               ctypes.byref(z), max_constraint_degree, coll, ctypes.byref(out)))
     else:
         a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
-        if generic:
+        if preprocessed is not None:
+            pcs.check(pcs.lib.eon_prove_air_pp_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                                  preprocessed.handle, challenger.handle, ctypes.byref(out_pp),
+                                                  _p(a_out), _p(z_out)))
+        elif generic:
             if collective is not None:
                 raise ValueError("the generic AIR path is not lane-sharded")
             pcs.check(pcs.lib.eon_prove_air_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
@@ -346,5 +419,8 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     if collective is None:
         timings.pop("exchange partial quotients")
         timings.pop("assemble columns")
-    return Proof([tc], [qc[c:c + 1] for c in range(chunks)], [opened_trace, opened_quot], out.degree_bits, timings,
-                 alpha, zeta)
+    opened = [opened_trace, opened_quot]
+    if preprocessed is None:
+        return Proof([tc], [qc[c:c + 1] for c in range(chunks)], opened, out.degree_bits, timings, alpha, zeta)
+    opened.append(Opened(values=[[po[0], po[1]]], witnesses=[[pw[0], pw[1]]]))
+    return Proof([tc], [qc[c:c + 1] for c in range(chunks)], opened, out.degree_bits, timings, alpha, zeta, [pc])

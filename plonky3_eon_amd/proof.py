@@ -24,6 +24,8 @@ class Proof:
     timings_ms: dict = field(default_factory=dict)
     alpha: int | None = None  # the challenges used (canonical ints)
     zeta: int | None = None
+    # with preprocessed columns: the setup's commitment [(Wp, 8)]; their openings are opened[2]
+    preprocessed_commit: object = None
 
 
 def log_quotient_degree(max_constraint_degree: int) -> int:
