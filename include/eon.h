@@ -153,8 +153,9 @@ int eon_diag_clock_probe(eon_ctx* ctx, uint32_t launches, uint32_t iters, eon_cl
  * cases. */
 int eon_diag_prod_asm_check(eon_ctx* ctx, uint32_t n, uint32_t seed, uint32_t mismatches[3]);
 
-/* ABI version; bumped on any signature or struct-layout change (5: preprocessed columns in the
- * generic quotient, eon_air_program_create_pp / eon_quotient_values_pp_dev, additive; 4: the
+/* ABI version; bumped on any signature or struct-layout change (6: the LogUp lookup entry points
+ * eon_air_program_create_lk / eon_quotient_values_lk_dev / eon_lookup_permutation_dev, additive;
+ * 5: preprocessed columns in the generic quotient, eon_air_program_create_pp / eon_quotient_values_pp_dev, additive; 4: the
  * verifier pairings and their eon_g2_affine / eon_fq12 types; 3: eon_collective's all_to_all
  * field).  Bindings must check it at load time: a binding built against an older layout would pass
  * a shorter eon_collective. */
@@ -335,8 +336,11 @@ int eon_p2air_quotient_values_dev(eon_ctx* ctx, const eon_p2air* air, const eon_
  * the three selectors (symbolic_builder.rs:205-221); EON_SYM_PREPROCESSED a = column of the
  * preprocessed trace (< the program's preprocessed width), b = row offset, a degree-1 leaf like
  * EON_SYM_MAIN (symbolic_variable.rs:8-40; the folder's preprocessed window, folder.rs:25-40,
- * prover.rs:677).  Permutation (LogUp) and challenge variables are rejected (EON_E_ARG): the prove
- * path has no lookups (prover.rs:211-250 None branch). */
+ * prover.rs:677).  EON_SYM_PERMUTATION a = column of the permutation (LogUp running-sum) trace,
+ * b = row offset, a degree-1 leaf read from a third matrix; EON_SYM_CHALLENGE a = index of a
+ * permutation challenge, a degree-0 leaf (prover.rs:210-278, 630-676).  Both need a program made
+ * by eon_air_program_create_lk; eon_air_program_create and eon_air_program_create_pp answer
+ * EON_E_ARG to them. */
 enum {
     EON_SYM_CONSTANT = 0,
     EON_SYM_MAIN = 1,
@@ -379,6 +383,39 @@ int eon_air_program_create_pp(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t 
                               uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints,
                               uint32_t width, uint32_t preprocessed_width, uint32_t n_public,
                               eon_air_program** out);
+/* ---- LogUp lookups (lookup/src/logup.rs, lookup_traits.rs; local lookups, Challenge = Fr) -------
+ * The same for an AIR with lookups: `permutation_width` running-sum columns (one per lookup,
+ * LogUpGadget::num_aux_cols) and n_challenges = 2 * permutation_width challenges (num_challenges;
+ * lookup with auxiliary column c uses alpha = challenges[2c], beta = challenges[2c + 1]).  The
+ * nodes hold the AIR's constraints followed by the lookups' (AirLookupHandler::eval,
+ * lookup_traits.rs:257-269) and, as shared nodes of the same DAG, what generate_permutation
+ * evaluates per row (logup.rs:379-562): lookups[l] has n_terms consecutive entries of `terms`, each
+ * the node of one tuple's denominator alpha - fold(elements, beta) and the node of its (signed)
+ * multiplicity.  n_lookups is 0 (a program for eon_quotient_values_lk_dev only) or
+ * permutation_width.  EON_E_ARG: a permutation column >= permutation_width, a challenge index >=
+ * n_challenges, an auxiliary column >= permutation_width or used by two lookups (the reference's
+ * debug assert, logup.rs:398-410), n_challenges != 2 * permutation_width, a denominator or
+ * multiplicity that reaches a permutation leaf (symbolic_to_expr is unimplemented there,
+ * lookup_traits.rs:408) or a row selector (the reference evaluates selectors there as unnormalised
+ * 0 / 1 and warns; refused here).  With permutation_width = 0 this is eon_air_program_create_pp. */
+typedef struct {
+    uint32_t aux_column; /* Lookup::columns[0] */
+    uint32_t n_terms;    /* element tuples = multiplicities */
+} eon_lookup_desc;
+typedef struct {
+    uint32_t denominator;  /* node index */
+    uint32_t multiplicity; /* node index */
+} eon_lookup_term;
+int eon_air_program_create_lk(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
+                              uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints,
+                              uint32_t width, uint32_t preprocessed_width, uint32_t n_public,
+                              uint32_t permutation_width, uint32_t n_challenges, const eon_lookup_desc* lookups,
+                              uint32_t n_lookups, const eon_lookup_term* terms, eon_air_program** out);
+/* the permutation width, challenge count and lookup count the program was compiled for (0 unless
+ * made by eon_air_program_create_lk) */
+uint32_t eon_air_program_permutation_width(const eon_air_program* prog);
+uint32_t eon_air_program_num_challenges(const eon_air_program* prog);
+uint32_t eon_air_program_num_lookups(const eon_air_program* prog);
 void eon_air_program_destroy(eon_air_program* prog);
 /* the preprocessed width the program was compiled for (0 for eon_air_program_create) */
 uint32_t eon_air_program_preprocessed_width(const eon_air_program* prog);
@@ -403,6 +440,30 @@ int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog, const eon
 int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde,
                                const eon_fr* pre_lde, uint32_t log_n, uint32_t log_qd, const eon_fr* alpha,
                                const eon_fr* publics, uint32_t n_public, eon_fr* out);
+
+/* The same with the permutation trace on the same quotient domain (prover.rs:317-319, 630-670):
+ * `perm_lde` = 2^(log_n + log_qd) rows x permutation_width columns, read through the same row pair,
+ * and `challenges` = host array of n_challenges Fr (the program's count, EON_E_SHAPE otherwise).
+ * perm_lde must be non-NULL exactly when the program has permutation columns (EON_E_ARG otherwise);
+ * eon_quotient_values_pp_dev and eon_quotient_values_dev answer EON_E_ARG for such a program. */
+int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde,
+                               const eon_fr* pre_lde, const eon_fr* perm_lde, uint32_t log_n, uint32_t log_qd,
+                               const eon_fr* alpha, const eon_fr* publics, uint32_t n_public,
+                               const eon_fr* challenges, uint32_t n_challenges, eon_fr* out);
+/* LogUpGadget::generate_permutation (logup.rs:379-562) for a program with a lookup description:
+ * `trace` = the main trace (device, height x width, height a power of two), `pre_trace` = the
+ * preprocessed trace on the same (trace) domain, publics / challenges host arrays, perm_out =
+ * height x permutation_width (device, row-major).  Row i evaluates every tuple's denominator and
+ * multiplicity with local = row i, next = row (i + 1) mod height; contribution[i][l] = sum over
+ * lookup l's tuples of multiplicity / denominator (one field inversion per row, Montgomery's
+ * trick); perm[0][c] = 0 and perm[i + 1][c] = perm[i][c] + contribution[i][l] in l's auxiliary
+ * column c.  The last row's contribution is computed and not stored.  A zero denominator on any
+ * row (the reference panics, field/src/batch_inverse.rs:17-18) is EON_E_ARG with a message naming
+ * the lookup; perm_out is then unspecified.  pre_trace must be non-NULL when a tuple reads a
+ * preprocessed column and NULL when the program has no preprocessed columns (EON_E_ARG). */
+int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* trace,
+                               const eon_fr* pre_trace, uint64_t height, const eon_fr* publics, uint32_t n_public,
+                               const eon_fr* challenges, uint32_t n_challenges, eon_fr* perm_out);
 
 /* out[i] = sum_{j<k} coeffs[j] * in[j * rows + i] (device in/out, host coeffs, 1 <= k <= 64):
  * the combine step of the lane-sharded quotient -- every rank all-gathers the

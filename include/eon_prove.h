@@ -16,6 +16,8 @@
  *   eon_preprocessed PreprocessedProverData (eon-uni-stark/src/preprocessed.rs:12-24) from
  *                    setup_preprocessed (:47-94), and eon_prove_air_pp, the Some(preprocessed)
  *                    branch of prove_with_preprocessed (prover.rs:58-88, 190-208, 321-322, 431)
+ *   eon_prove_air_lk the Some(permutation) branch (prover.rs:210-278, 317-319, 427-437): local LogUp
+ *                    lookups, the permutation trace generated on the device
  *   eon_challenger   DuplexChallenger<Fr, Poseidon2Bn254<3>, 3, 2>
  *                    (challenger/src/duplex_challenger.rs, bn254/src/poseidon2.rs) on the host.
  * Conventions are eon.h's: 0 / negative EON_E_* codes (the reference panics), host outputs,
@@ -189,7 +191,53 @@ int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
                         const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp,
                         eon_challenger* challenger, eon_proof_pp* out, eon_fr* alpha_out, eon_fr* zeta_out);
 
-/* bumped on any signature or struct-layout change (4: the preprocessed surface above, additive) */
+/* ---- LogUp lookups (lookup/src/logup.rs; eon-uni-stark/tests/lookup_air.rs) ---------------------
+ * eon_proof_pp plus the permutation trace's commitment and openings (proof.rs
+ * commitments.permutation, opened_values.permutation_local / _next); Wq = the program's permutation
+ * width (one running-sum column per lookup).  The three arrays are untouched (and may be NULL) when
+ * the program has no lookups. */
+typedef struct {
+    eon_proof_pp pp;
+    eon_g1_affine* permutation_commit;    /* [Wq] */
+    eon_fr* permutation_opened;           /* [2][Wq]: values at zeta, zeta * h */
+    eon_g1_affine* permutation_witnesses; /* [2][Wq] */
+} eon_proof_lk;
+
+/* eon_prove_air_pp / eon_prove_air_pp_fs for a program with local lookups
+ * (eon_air_program_create_lk with a lookup description), the Some(permutation) branch of
+ * prove_with_preprocessed, in the reference's order: commit the trace; observe log_ext_degree,
+ * log_degree, Wp, the trace commitment, the preprocessed commitment, the public values
+ * (prover.rs:196-208); sample the 2 Wq permutation challenges (:214-216); generate_permutation on the
+ * device (:238-245, eon_lookup_permutation_dev); commit the permutation trace on the trace domain
+ * (:270) and observe its commitment (:273); alpha (:300); the trace, the permutation trace and the
+ * preprocessed data on the quotient domain (:315-322); quotient_values, commit_quotient, zeta; open
+ * the trace at {zeta, zeta h}, the permutation trace at {zeta, zeta h}, the quotient chunks at
+ * {zeta}, the preprocessed data at {zeta, zeta h} (:426-439).  Generating, committing and extending
+ * the permutation trace is counted in EON_STAGE_TRACE_LDE.
+ *   pp         NULL exactly when the program has no preprocessed columns (as eon_prove_air_pp)
+ *   pre_trace  the preprocessed trace on the trace domain (device, height x Wp), what the reference
+ *              takes from air.preprocessed_trace() next to the committed data (:220-224): required
+ *              when a lookup tuple reads a preprocessed column (EON_E_ARG otherwise), NULL when the
+ *              program has no preprocessed columns.  It is NOT checked against pp's commitment: a
+ *              proof made with another matrix does not verify.
+ *   challenges (eon_prove_air_lk) the 2 Wq permutation challenges, host; n_challenges must be the
+ *              program's count (EON_E_SHAPE)
+ *   challenges_out (eon_prove_air_lk_fs; host, nullable) receives the sampled ones, 2 Wq Fr
+ * A zero LogUp denominator on any row is EON_E_ARG (the reference panics).  A program without
+ * lookups proves exactly as eon_prove_air_pp; eon_prove_air[_pp][_fs] answer EON_E_ARG to a program
+ * with lookups.  Local lookups only: a global lookup spans several AIRs, and the reference's own
+ * single-AIR verifier passes no lookup_data (verifier.rs:498).  No sharding. */
+int eon_prove_air_lk(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                     const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp, const eon_fr* pre_trace,
+                     const eon_fr* challenges, uint32_t n_challenges, const eon_fr* alpha, const eon_fr* zeta,
+                     eon_proof_lk* out);
+int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                        const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp,
+                        const eon_fr* pre_trace, eon_challenger* challenger, eon_proof_lk* out,
+                        eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out);
+
+/* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
+ * surface above; both additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

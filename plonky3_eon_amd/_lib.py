@@ -23,7 +23,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 5  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 6  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -53,6 +53,14 @@ class eon_poseidon2_constants(ctypes.Structure):
 
 class eon_sym_node(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint32), ("a", ctypes.c_uint32), ("b", ctypes.c_uint32)]
+
+
+class eon_lookup_desc(ctypes.Structure):
+    _fields_ = [("aux_column", ctypes.c_uint32), ("n_terms", ctypes.c_uint32)]
+
+
+class eon_lookup_term(ctypes.Structure):
+    _fields_ = [("denominator", ctypes.c_uint32), ("multiplicity", ctypes.c_uint32)]
 
 
 class eon_air_program_stats(ctypes.Structure):
@@ -138,12 +146,19 @@ SIGNATURES = {
     "eon_p2air_quotient_values_dev": (_INT, [_P, _P, _P, _U32, _U32, _P, _P]),
     "eon_air_program_create": (_INT, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _U32, ctypes.POINTER(_P)]),
     "eon_air_program_create_pp": (_INT, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _U32, _U32, ctypes.POINTER(_P)]),
+    "eon_air_program_create_lk": (_INT, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _U32, _U32, _U32, _U32, _P, _U32, _P,
+                                         ctypes.POINTER(_P)]),
+    "eon_air_program_permutation_width": (_U32, [_P]),
+    "eon_air_program_num_challenges": (_U32, [_P]),
+    "eon_air_program_num_lookups": (_U32, [_P]),
     "eon_air_program_destroy": (None, [_P]),
     "eon_air_program_preprocessed_width": (_U32, [_P]),
     "eon_air_program_info": (_INT, [_P, _P]),
     "eon_air_program_log_quotient_degree": (_U32, [_P, _U32]),
     "eon_quotient_values_dev": (_INT, [_P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     "eon_quotient_values_pp_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
+    "eon_quotient_values_lk_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P, _U32, _P]),
+    "eon_lookup_permutation_dev": (_INT, [_P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P]),
     "eon_fr_lincomb_dev": (_INT, [_P, _P, _U32, _U64, _P, _P]),
     "eon_fourstep_twiddle_pack_dev": (_INT, [_P, _P, _U32, _U32, _U64, _U32, _U32, _P]),
 }

@@ -150,9 +150,13 @@ class AirProgram:
     ``air`` is any object with ``width()``, ``num_public_values()`` and ``eval(builder)`` on the
     EonAirBuilder surface (symbolic.SymbolicAirBuilder).  An AIR with preprocessed columns
     (``builder.preprocessed()``) also has ``preprocessed_width()``, or the width is given here;
-    their LDE is then a second matrix of ``quotient_values``."""
+    their LDE is then a second matrix of ``quotient_values``.  An AIR with lookups has
+    ``get_lookups()`` (symbolic.Lookup, symbolic.register_lookup): the LogUp constraints follow its
+    own, the program reads ``permutation_width`` running-sum columns (a third matrix) and
+    ``num_challenges`` challenges, and ``lookup_permutation`` generates the permutation trace."""
 
-    def __init__(self, air, ctx: Context | None = None, preprocessed_width: int | None = None):
+    def __init__(self, air, ctx: Context | None = None, preprocessed_width: int | None = None,
+                 permutation_width: int | None = None):
         from . import symbolic
 
         self.ctx = ctx or default_context(0)
@@ -162,8 +166,22 @@ class AirProgram:
         if preprocessed_width is None:
             preprocessed_width = air.preprocessed_width() if hasattr(air, "preprocessed_width") else 0
         self.preprocessed_width = int(preprocessed_width)
-        cs = symbolic.get_symbolic_constraints(air, self.preprocessed_width, self.n_public)
-        nodes, consts, roots = symbolic.serialize(cs)
+        gadget = symbolic.LogUpGadget
+        # an AIR without lookups may still read permutation columns and challenges it declares
+        # itself (permutation_width here or as a method): a program for quotient_values only
+        if permutation_width is None:
+            permutation_width = air.permutation_width() if hasattr(air, "permutation_width") else 0
+        cs, lookups, terms = symbolic.get_symbolic_constraints_and_lookups(
+            air, self.preprocessed_width, self.n_public, int(permutation_width),
+            int(permutation_width) * gadget.num_challenges)
+        if lookups:
+            permutation_width = len(lookups) * gadget.num_aux_cols
+        self.permutation_width = int(permutation_width)
+        self.num_challenges = self.permutation_width * gadget.num_challenges
+        # the constraints and the lookup terms as one DAG: the denominators are shared nodes
+        flat = [e for tl in terms for pair in tl for e in pair]
+        nodes, consts, roots = symbolic.serialize(list(cs) + flat)
+        roots, term_roots = roots[:len(cs)], roots[len(cs):]
         self.num_nodes = len(nodes)
         na = (_lib.eon_sym_node * max(1, len(nodes)))(*[_lib.eon_sym_node(*n) for n in nodes])
         from .field import ints_to_limbs
@@ -171,10 +189,21 @@ class AirProgram:
         ca = np.ascontiguousarray(ints_to_limbs(consts) if consts else np.zeros((1, 4), np.uint64))
         ra = np.ascontiguousarray(np.array(roots if roots else [0], dtype=np.uint32))
         h = ctypes.c_void_p()
-        self.ctx.check(self.ctx.lib.eon_air_program_create_pp(
-            self.ctx.handle, na, len(nodes), ca.ctypes.data_as(ctypes.c_void_p), len(consts),
-            ra.ctypes.data_as(ctypes.c_void_p), len(roots), self.width, self.preprocessed_width, self.n_public,
-            ctypes.byref(h)))
+        if self.permutation_width == 0:
+            self.ctx.check(self.ctx.lib.eon_air_program_create_pp(
+                self.ctx.handle, na, len(nodes), ca.ctypes.data_as(ctypes.c_void_p), len(consts),
+                ra.ctypes.data_as(ctypes.c_void_p), len(roots), self.width, self.preprocessed_width, self.n_public,
+                ctypes.byref(h)))
+        else:
+            la = (_lib.eon_lookup_desc * max(1, len(lookups)))(*[_lib.eon_lookup_desc(lk.columns[0], len(tl))
+                                                         for lk, tl in zip(lookups, terms)])
+            nt = len(term_roots) // 2
+            ta = (_lib.eon_lookup_term * max(1, nt))(*[_lib.eon_lookup_term(term_roots[2 * t], term_roots[2 * t + 1])
+                                                       for t in range(nt)])
+            self.ctx.check(self.ctx.lib.eon_air_program_create_lk(
+                self.ctx.handle, na, len(nodes), ca.ctypes.data_as(ctypes.c_void_p), len(consts),
+                ra.ctypes.data_as(ctypes.c_void_p), len(roots), self.width, self.preprocessed_width, self.n_public,
+                self.permutation_width, self.num_challenges, la, len(lookups), ta, ctypes.byref(h)))
         self._h = h
         st = _lib.eon_air_program_stats()
         self.ctx.check(self.ctx.lib.eon_air_program_info(h, ctypes.byref(st)))
@@ -189,9 +218,34 @@ class AirProgram:
     def log_quotient_degree(self, is_zk: int = 0) -> int:
         return int(self.ctx.lib.eon_air_program_log_quotient_degree(self._h, is_zk))
 
-    def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=(), preprocessed_lde=None):
+    def lookup_permutation(self, trace, challenges, publics=(), preprocessed_trace=None):
+        """LogUpGadget::generate_permutation (logup.rs:379-562) on the device: `trace` (N, width, 4),
+        `challenges` num_challenges canonical ints, `preprocessed_trace` (N, preprocessed_width, 4)
+        on the trace domain when a lookup reads it -> the (N, permutation_width, 4) running sums."""
+        import torch
+
+        n = int(trace.shape[0])
+        out = torch.empty((n, self.permutation_width, 4), dtype=torch.int64, device=trace.device)
+        pub = _publics_limbs(publics)
+        ch = _publics_limbs(challenges)
+        pre = None
+        if preprocessed_trace is not None:
+            pre = preprocessed_trace.contiguous()
+            if pre.device != trace.device or tuple(pre.shape) != (n, self.preprocessed_width, 4):
+                raise ValueError(f"preprocessed_trace must be ({n}, {self.preprocessed_width}, 4) on {trace.device}")
+        self.ctx.set_stream(torch.cuda.current_stream(trace.device).cuda_stream)
+        self.ctx.check(self.ctx.lib.eon_lookup_permutation_dev(
+            self.ctx.handle, self._h, _dp(trace.contiguous()), _dp(pre) if pre is not None else None, n,
+            pub.ctypes.data_as(ctypes.c_void_p), len(publics), ch.ctypes.data_as(ctypes.c_void_p), len(challenges),
+            _dp(out)))
+        return out
+
+    def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=(), preprocessed_lde=None,
+                        permutation_lde=None, challenges=()):
         """quotient_values (prover.rs:539-709) on the trace's LDE over GENERATOR * K (natural);
-        `preprocessed_lde`: the preprocessed trace on the same domain, (Q, preprocessed_width, 4)."""
+        `preprocessed_lde`: the preprocessed trace on the same domain, (Q, preprocessed_width, 4);
+        `permutation_lde`: the permutation trace likewise, (Q, permutation_width, 4), with the
+        permutation `challenges` (canonical ints)."""
         import torch
 
         from .field import fr_to_abi
@@ -201,6 +255,22 @@ class AirProgram:
         a = fr_to_abi(alpha)
         pub = _publics_limbs(publics)
         self.ctx.set_stream(torch.cuda.current_stream(lde.device).cuda_stream)
+        if permutation_lde is not None or len(challenges):
+            mats = []
+            for name, m, w in (("preprocessed_lde", preprocessed_lde, self.preprocessed_width),
+                               ("permutation_lde", permutation_lde, self.permutation_width)):
+                if m is not None:
+                    m = m.contiguous()
+                    if m.device != lde.device or tuple(m.shape) != (q, w, 4):
+                        raise ValueError(f"{name} must be ({q}, {w}, 4) on {lde.device}")
+                mats.append(m)
+            ch = _publics_limbs(challenges)
+            self.ctx.check(self.ctx.lib.eon_quotient_values_lk_dev(
+                self.ctx.handle, self._h, _dp(lde.contiguous()), _dp(mats[0]) if mats[0] is not None else None,
+                _dp(mats[1]) if mats[1] is not None else None, log_n, log_qd, ctypes.byref(a),
+                pub.ctypes.data_as(ctypes.c_void_p), len(publics), ch.ctypes.data_as(ctypes.c_void_p),
+                len(challenges), _dp(out)))
+            return out
         if preprocessed_lde is None:
             self.ctx.check(self.ctx.lib.eon_quotient_values_dev(
                 self.ctx.handle, self._h, _dp(lde.contiguous()), log_n, log_qd, ctypes.byref(a),

@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <vector>
 
@@ -141,14 +142,20 @@ struct MemRegs {
 // PRE: the program reads preprocessed columns.  Without them the kernel is the one-matrix kernel,
 // instruction for instruction (the second matrix's compare and select are compiled out: measured at
 // +1 % on the Poseidon2-AIR when left in)
-template <bool PRE>
+// PERM: the program reads permutation (LogUp running-sum) columns, a third matrix through the same
+// row pair: a local / next index >= W + Wp is permutation column index - (W + Wp).  Compiled out
+// likewise when absent.
+template <bool PRE, bool PERM = false>
 struct Window {
-    static constexpr bool has_pre = PRE;
+    static constexpr bool has_pre = PRE, has_perm = PERM, terms = false;
     const Fr* local;
     const Fr* next;
     const Fr* pre_local;  // the preprocessed matrix's row pair (PRE only)
     const Fr* pre_next;
+    const Fr* perm_local;  // the permutation matrix's row pair (PERM only)
+    const Fr* perm_next;
     uint32_t width;       // main width W: a local / next index >= W is preprocessed column index - W
+    uint32_t perm_base;   // W + Wp (PERM only)
     const F29* table;  // program constants, then public values: x 2^261 (< 2p), converted on the host
     const Fr* sels;   // is_first_row | is_last_row | is_transition, q each (null if unused)
     uint64_t row, q;
@@ -206,11 +213,21 @@ __device__ __forceinline__ F29 fetch(uint32_t opnd, const RF& rf, const F29& pre
     // local / next row cell (of the main or the preprocessed matrix: the index is uniform, so
     // which one is a scalar compare) or a selector: the address picked by the (uniform) mode, one
     // load
-    const bool pre = Win::has_pre && i >= w.width;
-    const uint32_t col = pre ? i - w.width : i;
-    const Fr* p = m == M_LOCAL ? (pre ? w.pre_local : w.local) + col
-                  : m == M_NEXT ? (pre ? w.pre_next : w.next) + col
-                                : w.sels + (uint64_t)(m - M_FIRST) * w.q + w.row;
+    const Fr* p;
+    if constexpr (Win::has_perm) {
+        const bool perm = i >= w.perm_base;
+        const bool pre = Win::has_pre && !perm && i >= w.width;
+        const uint32_t col = perm ? i - w.perm_base : pre ? i - w.width : i;
+        p = m == M_LOCAL ? (perm ? w.perm_local : pre ? w.pre_local : w.local) + col
+            : m == M_NEXT ? (perm ? w.perm_next : pre ? w.pre_next : w.next) + col
+                          : w.sels + (uint64_t)(m - M_FIRST) * w.q + w.row;
+    } else {
+        const bool pre = Win::has_pre && i >= w.width;
+        const uint32_t col = pre ? i - w.width : i;
+        p = m == M_LOCAL ? (pre ? w.pre_local : w.local) + col
+            : m == M_NEXT ? (pre ? w.pre_next : w.next) + col
+                          : w.sels + (uint64_t)(m - M_FIRST) * w.q + w.row;
+    }
     return ld29(p, raw);
 }
 
@@ -232,6 +249,12 @@ __device__ __forceinline__ void exec1(const Instr& in, RF& rf, const Win& w, con
     const uint32_t opc = in.op & OP_MASK;
     if (opc == OP_NOP) return;
     const F29 x = fetch(in.a, rf, prev, hot, w);
+    if constexpr (Win::terms) {  // the term program (lookup terms): an ASSERT emits root K
+        if (opc == OP_ASSERT) {
+            w.emit(in.op >> K_SHIFT, x);
+            return;
+        }
+    }
     if (opc == OP_ASSERT) {  // folder.rs:81-85, alpha powers reversed
         const uint32_t kind = in.op >> K_SHIFT;
         if (kind == AS_PAIR)  // acc < 34p, pend < 32p: acc alpha^2 + pend alpha < 132 p^2
@@ -300,10 +323,13 @@ __device__ __forceinline__ void run_program(const CodeBlock* __restrict__ code, 
 
 // MODE 0: registers in LDS; 1: in the global buffer `gregs` (n_regs 36-byte registers per row).
 // PRE: with the preprocessed matrix `pre_lde` (pre_width columns); otherwise both are unused.
-template <int MODE, bool PRE>
+// PERM: with the permutation matrix `perm_lde` (perm_width columns), likewise (a program with
+// permutation columns runs the PRE instance whatever its preprocessed width).
+template <int MODE, bool PRE, bool PERM>
 __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __restrict__ code, uint32_t n_blocks,
                                                       uint32_t n_regs, const Fr* __restrict__ lde, uint32_t width,
                                                       const Fr* __restrict__ pre_lde, uint32_t pre_width,
+                                                      const Fr* __restrict__ perm_lde, uint32_t perm_width,
                                                       uint64_t q, uint64_t next_step, const F29* __restrict__ table,
                                                       const Fr* __restrict__ sels, const Fr* __restrict__ inv_van,
                                                       uint32_t nr_mask, Fr alpha, Fr* __restrict__ out,
@@ -312,12 +338,15 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= q) return;
     const uint64_t next_row = (row + next_step) & (q - 1);
-    Window<PRE> w{lde + row * width,
-                  lde + next_row * width,
-                  PRE ? pre_lde + row * pre_width : nullptr,
-                  PRE ? pre_lde + next_row * pre_width : nullptr,
-                  width,
-                  table,
+    Window<PRE, PERM> w{lde + row * width,
+                        lde + next_row * width,
+                        PRE ? pre_lde + row * pre_width : nullptr,
+                        PRE ? pre_lde + next_row * pre_width : nullptr,
+                        PERM ? perm_lde + row * perm_width : nullptr,
+                        PERM ? perm_lde + next_row * perm_width : nullptr,
+                        width,
+                        PERM ? width + pre_width : 0,
+                        table,
                   sels,
                   row,
                   q};
@@ -342,12 +371,83 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
     st_vec(out + row, pack29<FrP>(canon29<FrP>(r)));
 }
 
+// ---- LogUp permutation trace: per-row contributions (generate_permutation, lookup/src/logup.rs:379-562)
+// The term program runs on the TRACE domain: local = row i, next = row (i + 1) mod height, no
+// selectors, no permutation columns.  Its k-th root is emitted (not folded) as register k of a
+// MemRegs file in global memory, in the interpreter's own form (x 2^261, < 32p): planes of `height`
+// rows, so a wave's stores are contiguous.  lookup.hip brings them to canonical form.
+template <bool PRE>
+struct TermWindow {
+    static constexpr bool has_pre = PRE, has_perm = false, terms = true;
+    const Fr* local;
+    const Fr* next;
+    const Fr* pre_local;
+    const Fr* pre_next;
+    uint32_t width;
+    const F29* table;  // program constants, public values, challenges
+    const Fr* sels;    // never read (a term that reaches a selector is refused at compile time); a valid address
+    uint64_t row, q;
+    MemRegs out;  // this row's view of the emitted values
+    __device__ __forceinline__ void emit(uint32_t k, const F29& x) const {
+        MemRegs o = out;
+        o.set(k, x);
+    }
+};
+
+// One thread per trace row: the term program writes the row's denominators (plane 2t) and
+// multiplicities (plane 2t + 1); lookup.hip inverts and sums them.
+template <int MODE, bool PRE>
+__global__ void __launch_bounds__(AIR_BLOCK) k_lookup_terms(const CodeBlock* __restrict__ code, uint32_t n_blocks,
+                                                        uint32_t n_regs, const Fr* __restrict__ trace, uint32_t width,
+                                                        const Fr* __restrict__ pre, uint32_t pre_width,
+                                                        uint64_t height, const F29* __restrict__ table,
+                                                        uint32_t n_out, uint4* __restrict__ planes,
+                                                        uint4* __restrict__ gregs) {
+    extern __shared__ uint4 lds_regs[];
+    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= height) return;
+    const uint64_t next_row = row + 1 == height ? 0 : row + 1;
+    TermWindow<PRE> w{trace + row * width,
+                      trace + next_row * width,
+                      PRE ? pre + row * pre_width : nullptr,
+                      PRE ? pre + next_row * pre_width : nullptr,
+                      width,
+                      table,
+                      trace,
+                      row,
+                      height,
+                      MemRegs{planes + row, reinterpret_cast<uint32_t*>(planes + 2ull * n_out * height) + row, height}};
+    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
+    MemRegs rf;
+    if (MODE == 0) {
+        rf.base = lds_regs + threadIdx.x;
+        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x) + threadIdx.x;
+        rf.stride = blockDim.x;
+    } else {
+        rf.base = gregs + row;
+        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem * height) + row;
+        rf.stride = height;
+    }
+    F29 acc, zero;
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc.l[i] = zero.l[i] = 0;
+    run_program(code, n_blocks, rf, w, zero, acc);
+}
+
 }  // namespace
 
 struct eon_air_program {
     eon_ctx* ctx = nullptr;
     uint32_t width = 0, pre_width = 0, n_public = 0, n_constraints = 0, max_degree = 0, n_regs = 0, n_consts = 0;
+    uint32_t perm_width = 0, n_challenges = 0;
     bool uses_sels = false;
+    // lookups (eon_air_program_create_lk): lookup l's terms are [term_off[l], term_off[l + 1]) and
+    // its running sum is permutation column aux[l]; `terms` is the term program, whose k-th root
+    // (an OP_ASSERT with K = k) is the denominator (k even) or the multiplicity (k odd) of term k / 2
+    std::vector<uint32_t> term_off, aux;
+    std::unique_ptr<eon_air_program> terms;
+    bool terms_read_pre = false;
+    DevBuf d_desc, d_terms, d_flag;
     std::vector<Instr> code;
     std::vector<Fr> consts;
     DevBuf d_code, d_table, d_sels, d_regs;
@@ -362,17 +462,49 @@ int finish(eon_ctx* ctx, const Status& s) {
     return s.code;
 }
 
-struct Leaf {
-    uint32_t kind, a, b;
-};
+// the constant table of a launch: program constants ++ public values ++ challenges, in the device's
+// form
+Status stage_table(eon_ctx* ctx, eon_air_program* prog, const eon_fr* publics, uint32_t n_public,
+                   const eon_fr* challenges, uint32_t n_challenges) {
+    prog->staged.assign(prog->consts.begin(), prog->consts.end());
+    for (uint32_t i = 0; i < n_public; i++) {
+        const Fr v = fr_from_abi(&publics[i]);
+        if (!fr_is_canonical(v)) return Status::err(EON_E_ARG, "public value is not a canonical Fr");
+        prog->staged.push_back(v);
+    }
+    for (uint32_t i = 0; i < n_challenges; i++) {
+        const Fr v = fr_from_abi(&challenges[i]);
+        if (!fr_is_canonical(v)) return Status::err(EON_E_ARG, "challenge is not a canonical Fr");
+        prog->staged.push_back(v);
+    }
+    if (!prog->staged.empty()) {
+        prog->staged29.resize(prog->staged.size());
+        for (size_t i = 0; i < prog->staged.size(); i++) prog->staged29[i] = shl5_to261<FrP>(prog->staged[i]);
+        EON_HIP(hipMemcpyAsync(prog->d_table.p, prog->staged29.data(), prog->staged29.size() * sizeof(F29),
+                               hipMemcpyHostToDevice, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));  // `staged` is reused by the next launch
+    }
+    return Status::ok();
+}
+
+void release_program(eon_air_program* p) {
+    for (DevBuf* b : {&p->d_code, &p->d_table, &p->d_sels, &p->d_regs, &p->d_desc, &p->d_terms, &p->d_flag})
+        b->release();
+    if (p->terms) release_program(p->terms.get());
+}
 
 // compile nodes -> program; see the file comment
+// term_mode: the roots are lookup terms, not constraints: root k's OP_ASSERT carries K = k (the
+// kernel emits the value instead of folding it), and the roots may reach neither a permutation leaf
+// nor a selector (*reads_pre: whether they reach a preprocessed leaf)
 Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
-               uint32_t n_consts, const uint32_t* roots, uint32_t n_roots) {
+               uint32_t n_consts, const uint32_t* roots, uint32_t n_roots, bool term_mode = false,
+               bool* reads_pre = nullptr) {
     // operand indices are 28 bits (bit 28 is OPND_RAW): a wider main-column index, constant slot
     // or public slot would set the raw flag and read the wrong leaf
     // (the preprocessed columns share the local / next index space, after the main ones)
-    if ((uint64_t)p->width + p->pre_width > IDX_MASK || (uint64_t)n_consts + p->n_public > IDX_MASK)
+    if ((uint64_t)p->width + p->pre_width + p->perm_width > IDX_MASK ||
+        (uint64_t)n_consts + p->n_public + p->n_challenges > IDX_MASK)
         return Status::err(EON_E_SHAPE, "trace width (main + preprocessed) and constant + public slots must each "
                                         "be < 2^28");
     // value numbering
@@ -469,10 +601,28 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
                 vn[i] = intern(LEAF, (nd.b ? M_NEXT : M_LOCAL) << 29 | (p->width + nd.a), 0);
                 degree[i] = 1;
                 break;
-            case EON_SYM_PERMUTATION:
-            case EON_SYM_CHALLENGE:
-                return Status::err(EON_E_ARG, "permutation (LogUp) / challenge variables are not supported by the "
-                                              "generic quotient program");
+            case EON_SYM_PERMUTATION:  // a trace leaf of the third matrix: index W + Wp + column
+                if (p->perm_width == 0)
+                    return Status::err(EON_E_ARG, "permutation (LogUp) variables need a program with permutation "
+                                                  "columns (eon_air_program_create_lk)");
+                if (nd.a >= p->perm_width || nd.b > 1)
+                    return Status::err(EON_E_ARG, "permutation variable out of range (column " + std::to_string(nd.a) +
+                                                      ", offset " + std::to_string(nd.b) + ", permutation width " +
+                                                      std::to_string(p->perm_width) + ")");
+                vn[i] = intern(LEAF, (nd.b ? M_NEXT : M_LOCAL) << 29 | (p->width + p->pre_width + nd.a), 0);
+                degree[i] = 1;
+                break;
+            case EON_SYM_CHALLENGE:  // a run-time constant after the public values
+                if (nd.a >= p->n_challenges)
+                    return Status::err(EON_E_ARG, p->n_challenges == 0
+                                                      ? "challenge variables need a program with permutation "
+                                                        "challenges (eon_air_program_create_lk)"
+                                                      : "challenge index " + std::to_string(nd.a) +
+                                                            " out of range (" + std::to_string(p->n_challenges) +
+                                                            " challenges)");
+                vn[i] = intern(LEAF, 0xffffffffu, p->n_public + nd.a);  // resolved to a table slot below
+                degree[i] = 0;
+                break;
             default:
                 return Status::err(EON_E_ARG, "unknown node kind " + std::to_string(nd.kind));
         }
@@ -488,8 +638,34 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
         }
     p->max_degree = 0;
     for (uint32_t k = 0; k < n_roots; k++) {
-        if (roots[k] >= n_nodes) return Status::err(EON_E_ARG, "constraint index out of range");
+        if (roots[k] >= n_nodes)
+            return Status::err(EON_E_ARG, term_mode ? "lookup term index out of range" : "constraint index out of range");
         p->max_degree = std::max(p->max_degree, degree[roots[k]]);
+    }
+    if (term_mode) {  // what the terms reach
+        if (n_roots >= (1u << (32 - K_SHIFT))) return Status::err(EON_E_SHAPE, "more than 2^23 - 1 lookup terms");
+        std::vector<char> seen_v(vals.size(), 0);
+        std::vector<uint32_t> st;
+        for (uint32_t k = 0; k < n_roots; k++) st.push_back(vn[roots[k]]);
+        p->uses_sels = false;
+        while (!st.empty()) {
+            const uint32_t v = st.back();
+            st.pop_back();
+            if (seen_v[v]) continue;
+            seen_v[v] = 1;
+            if (vals[v].op != LEAF) {
+                st.push_back(vals[v].a);
+                if (vals[v].op != OP_NEG) st.push_back(vals[v].b);
+                continue;
+            }
+            const uint32_t m = vals[v].a >> 29, idx = vals[v].a & IDX_MASK;
+            if (m == M_FIRST || m == M_LAST || m == M_TRANS)
+                return Status::err(EON_E_ARG, "a lookup denominator or multiplicity reads a row selector: refused "
+                                              "(the reference evaluates selectors there as unnormalised 0 / 1)");
+            if ((m == M_LOCAL || m == M_NEXT) && idx >= p->width + p->pre_width)
+                return Status::err(EON_E_ARG, "a lookup denominator or multiplicity reads a permutation column");
+            if ((m == M_LOCAL || m == M_NEXT) && idx >= p->width && reads_pre) *reads_pre = true;
+        }
     }
     // schedule: per constraint, post-order of its not-yet-emitted values, then ASSERT
     const uint32_t nv = (uint32_t)vals.size();
@@ -592,7 +768,8 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
         const Item& it = items[t];
         if (it.assert_) {  // constraint values: < B_RAW p (raw leaf) or < B_MAX p
             const uint32_t odd = n_asserts & 1;
-            const uint32_t kind = (odd && seen == 0) ? AS_INIT : ((seen - odd) % 2 == 0 ? AS_PEND : AS_PAIR);
+            const uint32_t kind =
+                term_mode ? seen : (odd && seen == 0) ? AS_INIT : ((seen - odd) % 2 == 0 ? AS_PEND : AS_PAIR);
             seen++;
             p->code.push_back({OP_ASSERT | kind << K_SHIFT, 0, opnd(it.v) | (is_tleaf(it.v) ? OPND_RAW : 0u), 0});
             release(it.v, t);
@@ -660,43 +837,108 @@ Status compile(eon_air_program* p, const eon_sym_node* nodes, uint32_t n_nodes, 
 
 extern "C" {
 
-int eon_air_program_create_pp(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
+int eon_air_program_create_lk(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
                               uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints, uint32_t width,
-                              uint32_t preprocessed_width, uint32_t n_public, eon_air_program** out) {
+                              uint32_t preprocessed_width, uint32_t n_public, uint32_t permutation_width,
+                              uint32_t n_challenges, const eon_lookup_desc* lookups, uint32_t n_lookups,
+                              const eon_lookup_term* terms, eon_air_program** out) {
     if (!ctx) return EON_E_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
     Status s = [&]() -> Status {
-        if (!out || (n_nodes && !nodes) || (n_consts && !consts) || (n_constraints && !constraints))
+        if (!out || (n_nodes && !nodes) || (n_consts && !consts) || (n_constraints && !constraints) ||
+            (n_lookups && !lookups))
             return Status::err(EON_E_ARG, "null argument");
-        auto* p = new eon_air_program();
+        // LogUp: one auxiliary column and two challenges per lookup (logup.rs:266-273, prover.rs:93-94)
+        if (n_challenges != 2 * (uint64_t)permutation_width)
+            return Status::err(EON_E_ARG, "n_challenges must be 2 * permutation_width (" +
+                                              std::to_string(n_challenges) + " challenges, permutation width " +
+                                              std::to_string(permutation_width) + ")");
+        if (n_lookups != 0 && n_lookups != permutation_width)
+            return Status::err(EON_E_ARG, "the lookup description must cover every permutation column (" +
+                                              std::to_string(n_lookups) + " lookups, permutation width " +
+                                              std::to_string(permutation_width) + ")");
+        auto p = std::make_unique<eon_air_program>();
         p->ctx = ctx;
         p->width = width;
         p->pre_width = preprocessed_width;
         p->n_public = n_public;
         p->n_constraints = n_constraints;
-        Status c = compile(p, nodes, n_nodes, consts, n_consts, constraints, n_constraints);
-        if (c.bad()) {
-            delete p;
-            return c;
+        p->perm_width = permutation_width;
+        p->n_challenges = n_challenges;
+        std::vector<uint32_t> term_roots;
+        {
+            std::vector<char> used(permutation_width, 0);
+            uint64_t t = 0;
+            for (uint32_t l = 0; l < n_lookups; l++) {
+                const uint32_t c = lookups[l].aux_column;
+                if (c >= permutation_width)
+                    return Status::err(EON_E_ARG, "lookup " + std::to_string(l) + ": auxiliary column " +
+                                                      std::to_string(c) + " >= permutation width " +
+                                                      std::to_string(permutation_width));
+                if (used[c])  // logup.rs:398-410
+                    return Status::err(EON_E_ARG, "duplicate aux column index " + std::to_string(c) + " across lookups");
+                used[c] = 1;
+                if (lookups[l].n_terms && !terms) return Status::err(EON_E_ARG, "null argument");
+                p->term_off.push_back((uint32_t)t);
+                p->aux.push_back(c);
+                for (uint32_t k = 0; k < lookups[l].n_terms; k++, t++) {
+                    term_roots.push_back(terms[t].denominator);
+                    term_roots.push_back(terms[t].multiplicity);
+                }
+                if (t >= (1u << 22)) return Status::err(EON_E_SHAPE, "more than 2^22 - 1 lookup terms");
+            }
+            if (n_lookups) p->term_off.push_back((uint32_t)t);
         }
-        // device copy padded with OP_NOP to whole CODE_BLOCKs
-        std::vector<Instr> padded(p->code);
-        while (padded.size() % CODE_BLOCK) padded.push_back({OP_NOP, NO_DST, M_PREV << 29, 0});
-        hipError_t e = p->d_code.ensure(std::max<size_t>(1, padded.size()) * sizeof(Instr));
-        if (e == hipSuccess && !padded.empty())
-            e = hipMemcpy(p->d_code.p, padded.data(), padded.size() * sizeof(Instr), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = p->d_table.ensure(std::max<size_t>(1, p->n_consts + n_public) * sizeof(F29));
+        EON_TRY(compile(p.get(), nodes, n_nodes, consts, n_consts, constraints, n_constraints));
+        if (n_lookups) {
+            p->terms = std::make_unique<eon_air_program>();
+            eon_air_program* t = p->terms.get();
+            t->ctx = ctx;
+            t->width = width;
+            t->pre_width = preprocessed_width;
+            t->n_public = n_public;
+            t->perm_width = permutation_width;
+            t->n_challenges = n_challenges;
+            EON_TRY(compile(t, nodes, n_nodes, consts, n_consts, term_roots.data(), (uint32_t)term_roots.size(), true,
+                            &p->terms_read_pre));
+        }
+        // device copies padded with OP_NOP to whole CODE_BLOCKs
+        auto upload = [&](eon_air_program* q) -> hipError_t {
+            std::vector<Instr> padded(q->code);
+            while (padded.size() % CODE_BLOCK) padded.push_back({OP_NOP, NO_DST, M_PREV << 29, 0});
+            hipError_t e = q->d_code.ensure(std::max<size_t>(1, padded.size()) * sizeof(Instr));
+            if (e == hipSuccess && !padded.empty())
+                e = hipMemcpy(q->d_code.p, padded.data(), padded.size() * sizeof(Instr), hipMemcpyHostToDevice);
+            if (e == hipSuccess)
+                e = q->d_table.ensure(std::max<size_t>(1, q->n_consts + n_public + n_challenges) * sizeof(F29));
+            return e;
+        };
+        hipError_t e = upload(p.get());
+        if (e == hipSuccess && p->terms) e = upload(p->terms.get());
+        if (e == hipSuccess && p->terms) {
+            std::vector<uint32_t> desc(p->term_off);
+            desc.insert(desc.end(), p->aux.begin(), p->aux.end());
+            e = p->d_desc.ensure(desc.size() * sizeof(uint32_t));
+            if (e == hipSuccess)
+                e = hipMemcpy(p->d_desc.p, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = p->d_flag.ensure(sizeof(uint32_t));
+        }
         if (e != hipSuccess) {
-            p->d_code.release();
-            p->d_table.release();
-            delete p;
+            release_program(p.get());
             EON_HIP(e);
         }
-        *out = p;
+        *out = p.release();
         return Status::ok();
     }();
     return finish(ctx, s);
+}
+
+int eon_air_program_create_pp(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
+                              uint32_t n_consts, const uint32_t* constraints, uint32_t n_constraints, uint32_t width,
+                              uint32_t preprocessed_width, uint32_t n_public, eon_air_program** out) {
+    return eon_air_program_create_lk(ctx, nodes, n_nodes, consts, n_consts, constraints, n_constraints, width,
+                                     preprocessed_width, n_public, 0, 0, nullptr, 0, nullptr, out);
 }
 
 int eon_air_program_create(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
@@ -711,7 +953,7 @@ void eon_air_program_destroy(eon_air_program* p) {
     std::lock_guard<std::mutex> lk(p->ctx->mu);
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    for (DevBuf* b : {&p->d_code, &p->d_table, &p->d_sels, &p->d_regs}) b->release();
+    release_program(p);
     delete p;
 }
 
@@ -728,6 +970,9 @@ int eon_air_program_info(const eon_air_program* p, eon_air_program_stats* out) {
 }
 
 uint32_t eon_air_program_preprocessed_width(const eon_air_program* p) { return p ? p->pre_width : 0; }
+uint32_t eon_air_program_permutation_width(const eon_air_program* p) { return p ? p->perm_width : 0; }
+uint32_t eon_air_program_num_challenges(const eon_air_program* p) { return p ? p->n_challenges : 0; }
+uint32_t eon_air_program_num_lookups(const eon_air_program* p) { return p ? (uint32_t)p->aux.size() : 0; }
 
 uint32_t eon_air_program_log_quotient_degree(const eon_air_program* p, uint32_t is_zk) {
     // symbolic_builder.rs:28-42: log2_ceil(max(max_degree + is_zk, 2) - 1)
@@ -738,16 +983,25 @@ uint32_t eon_air_program_log_quotient_degree(const eon_air_program* p, uint32_t 
     return b;
 }
 
-int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* lde, const eon_fr* pre_lde,
-                               uint32_t log_n, uint32_t log_qd, const eon_fr* alpha, const eon_fr* publics,
-                               uint32_t n_public, eon_fr* out) {
+int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* lde, const eon_fr* pre_lde,
+                               const eon_fr* perm_lde, uint32_t log_n, uint32_t log_qd, const eon_fr* alpha,
+                               const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
+                               uint32_t n_challenges, eon_fr* out) {
     if (!ctx || !prog_c) return EON_E_ARG;
     auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
     Status s = [&]() -> Status {
-        if (!lde || !alpha || !out || (n_public && !publics)) return Status::err(EON_E_ARG, "null argument");
+        if (!lde || !alpha || !out || (n_public && !publics) || (n_challenges && !challenges))
+            return Status::err(EON_E_ARG, "null argument");
         if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+        if ((perm_lde != nullptr) != (prog->perm_width > 0))
+            return Status::err(EON_E_ARG, prog->perm_width > 0
+                                              ? "the program reads permutation columns: perm_lde must not be null "
+                                                "(eon_quotient_values_lk_dev)"
+                                              : "the program has no permutation columns: perm_lde must be null");
+        if (n_challenges != prog->n_challenges)
+            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
         if ((pre_lde != nullptr) != (prog->pre_width > 0))
             return Status::err(EON_E_ARG, prog->pre_width > 0
                                               ? "the program reads preprocessed columns: pre_lde must not be null"
@@ -759,20 +1013,7 @@ int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
         const Fr al = fr_from_abi(alpha);
         if (!fr_is_canonical(al)) return Status::err(EON_E_ARG, "alpha is not a canonical Fr");
         const uint64_t q = 1ull << log_q;
-        // constant table = program constants ++ public values
-        prog->staged.assign(prog->consts.begin(), prog->consts.end());
-        for (uint32_t i = 0; i < n_public; i++) {
-            const Fr v = fr_from_abi(&publics[i]);
-            if (!fr_is_canonical(v)) return Status::err(EON_E_ARG, "public value is not a canonical Fr");
-            prog->staged.push_back(v);
-        }
-        if (!prog->staged.empty()) {
-            prog->staged29.resize(prog->staged.size());
-            for (size_t i = 0; i < prog->staged.size(); i++) prog->staged29[i] = shl5_to261<FrP>(prog->staged[i]);
-            EON_HIP(hipMemcpyAsync(prog->d_table.p, prog->staged29.data(), prog->staged29.size() * sizeof(F29),
-                                   hipMemcpyHostToDevice, ctx->stream));
-            EON_HIP(hipStreamSynchronize(ctx->stream));  // `staged` is reused by the next launch
-        }
+        EON_TRY(stage_table(ctx, prog, publics, n_public, challenges, n_challenges));
         // quotient domain = trace domain (shift 1).create_disjoint_domain: shift GENERATOR
         // (commit/src/domain.rs:155-168); selectors_on_coset over it (prover.rs:563-564)
         const Fr g5 = from_u64<FrP>(5);
@@ -810,7 +1051,8 @@ int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
             const uint32_t opc = in.op & OP_MASK;
             products += (opc == OP_MUL || opc == OP_SQR || opc == OP_ASSERT) ? 1 : 0;
         }
-        ctx->prof.begin("k_air_quotient", q * ((uint64_t)prog->width + prog->pre_width) * 32 + q * 32, ctx->stream,
+        ctx->prof.begin("k_air_quotient",
+                        q * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32 + q * 32, ctx->stream,
                         q * products);
         const CodeBlock* code = prog->d_code.as<CodeBlock>();
         const uint32_t n_blocks = (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK);
@@ -818,16 +1060,22 @@ int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
         const Fr* sel = prog->uses_sels ? prog->d_sels.as<Fr>() : nullptr;
         Fr* out_f = reinterpret_cast<Fr*>(out);
         using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
-                                  uint64_t, uint64_t, const F29*, const Fr*, const Fr*, uint32_t, Fr, Fr*, uint4*);
-        const bool has_pre = prog->pre_width > 0;
-        const KernelFn kern = mode == 0 ? (has_pre ? k_air_quotient<0, true> : k_air_quotient<0, false>)
-                                        : (has_pre ? k_air_quotient<1, true> : k_air_quotient<1, false>);
+                                  const Fr*, uint32_t, uint64_t, uint64_t, const F29*, const Fr*, const Fr*, uint32_t,
+                                  Fr, Fr*, uint4*);
+        const bool has_pre = prog->pre_width > 0, has_perm = prog->perm_width > 0;
+        const KernelFn kern = mode == 0 ? (has_perm  ? k_air_quotient<0, true, true>
+                                           : has_pre ? k_air_quotient<0, true, false>
+                                                     : k_air_quotient<0, false, false>)
+                                        : (has_perm  ? k_air_quotient<1, true, true>
+                                           : has_pre ? k_air_quotient<1, true, false>
+                                                     : k_air_quotient<1, false, false>);
         if (mode == 0)  // per launch: the attribute is per device, and this context's device may
                         // differ from the one another context set it on
             EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, ctx->stream, code, n_blocks, prog->n_regs, lde_f,
-                           prog->width, reinterpret_cast<const Fr*>(pre_lde), prog->pre_width, q, 1ull << log_qd,
+                           prog->width, reinterpret_cast<const Fr*>(pre_lde), prog->pre_width,
+                           reinterpret_cast<const Fr*>(perm_lde), prog->perm_width, q, 1ull << log_qd,
                            prog->d_table.as<F29>(), sel, inv_van, nr_mask, al, out_f,
                            mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
         ctx->prof.end(ctx->stream);
@@ -835,6 +1083,19 @@ int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
         return Status::ok();
     }();
     return finish(ctx, s);
+}
+
+int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde, const eon_fr* pre_lde,
+                               uint32_t log_n, uint32_t log_qd, const eon_fr* alpha, const eon_fr* publics,
+                               uint32_t n_public, eon_fr* out) {
+    if (!ctx || !prog) return EON_E_ARG;
+    if (prog->perm_width > 0 || prog->n_challenges > 0) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        return finish(ctx, Status::err(EON_E_ARG, "the program reads permutation columns and challenges: call "
+                                                  "eon_quotient_values_lk_dev with perm_lde and the challenges"));
+    }
+    return eon_quotient_values_lk_dev(ctx, prog, lde, pre_lde, nullptr, log_n, log_qd, alpha, publics, n_public,
+                                      nullptr, 0, out);
 }
 
 int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde, uint32_t log_n,
@@ -847,6 +1108,80 @@ int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog, const eon
                                                   "eon_quotient_values_pp_dev with their LDE"));
     }
     return eon_quotient_values_pp_dev(ctx, prog, lde, nullptr, log_n, log_qd, alpha, publics, n_public, out);
+}
+
+int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* trace,
+                               const eon_fr* pre_trace, uint64_t height, const eon_fr* publics, uint32_t n_public,
+                               const eon_fr* challenges, uint32_t n_challenges, eon_fr* perm_out) {
+    if (!ctx || !prog_c) return EON_E_ARG;
+    auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (!trace || !perm_out || (n_public && !publics) || (n_challenges && !challenges))
+            return Status::err(EON_E_ARG, "null argument");
+        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+        if (!prog->terms)
+            return Status::err(EON_E_ARG, "the program carries no lookup description (eon_air_program_create_lk)");
+        if (prog->terms_read_pre != (pre_trace != nullptr) && (prog->terms_read_pre || prog->pre_width == 0))
+            return Status::err(EON_E_ARG, prog->terms_read_pre
+                                              ? "a lookup term reads a preprocessed column: pre_trace must not be null"
+                                              : "the program has no preprocessed columns: pre_trace must be null");
+        if (n_public != prog->n_public)
+            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
+        if (n_challenges != prog->n_challenges)
+            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
+        if (height == 0 || (height & (height - 1)) || height > (1ull << 28))
+            return Status::err(EON_E_SHAPE, "trace height must be a power of two <= 2^28");
+        eon_air_program* tp = prog->terms.get();
+        EON_TRY(stage_table(ctx, tp, publics, n_public, challenges, n_challenges));
+        const uint32_t n_lookups = (uint32_t)prog->aux.size(), n_terms = prog->term_off.back();
+        // per row: 2 T emitted values of 36 bytes (padded to 48 so the prefix planes stay aligned),
+        // then T prefix products
+        const uint64_t emitted = 2ull * n_terms * height * 48;
+        EON_HIP(ctx_ensure(ctx, prog->d_terms, std::max<uint64_t>(1, emitted + (uint64_t)n_terms * height * sizeof(Fr))));
+        EON_HIP(hipMemsetAsync(prog->d_flag.p, 0xff, sizeof(uint32_t), ctx->stream));
+        const uint64_t per_thread = (uint64_t)(tp->n_regs > AIR_VREGS ? tp->n_regs - AIR_VREGS : 0) * 36;
+        uint32_t block = AIR_BLOCK;
+        while (block > 64 && block * per_thread > 64 * 1024) block /= 2;
+        const int mode = block * per_thread <= 160 * 1024 ? 0 : 1;
+        if (mode != 0) block = AIR_BLOCK;
+        if (mode == 1) EON_HIP(tp->d_regs.ensure(std::max<uint64_t>(1, height * per_thread)));
+        const unsigned grid = (unsigned)((height + block - 1) / block);
+        const size_t shmem = mode == 0 ? (size_t)block * per_thread : 0;
+        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
+                                  uint64_t, const F29*, uint32_t, uint4*, uint4*);
+        const bool has_pre = pre_trace != nullptr && prog->pre_width > 0;
+        const KernelFn kern = mode == 0 ? (has_pre ? k_lookup_terms<0, true> : k_lookup_terms<0, false>)
+                                        : (has_pre ? k_lookup_terms<1, true> : k_lookup_terms<1, false>);
+        if (mode == 0)
+            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ctx->prof.begin("k_lookup_terms", height * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32,
+                        ctx->stream);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, ctx->stream, tp->d_code.as<CodeBlock>(),
+                           (uint32_t)((tp->code.size() + CODE_BLOCK - 1) / CODE_BLOCK), tp->n_regs,
+                           reinterpret_cast<const Fr*>(trace), prog->width, reinterpret_cast<const Fr*>(pre_trace),
+                           prog->pre_width, height, tp->d_table.as<F29>(), 2 * n_terms, prog->d_terms.as<uint4>(),
+                           mode == 1 ? tp->d_regs.as<uint4>() : nullptr);
+        ctx->prof.end(ctx->stream);
+        EON_HIP(hipGetLastError());
+        EON_TRY(lookup_contributions(ctx, prog->d_terms.as<uint4>(),
+                                     reinterpret_cast<Fr*>(prog->d_terms.as<char>() + emitted), height, prog->d_desc.as<uint32_t>(), n_lookups,
+                                     n_terms, reinterpret_cast<Fr*>(perm_out), prog->perm_width,
+                                     prog->d_flag.as<uint32_t>()));
+        EON_TRY(lookup_running_sum(ctx, reinterpret_cast<Fr*>(perm_out), height, prog->perm_width));
+        uint32_t flag = 0;
+        EON_HIP(hipMemcpyAsync(&flag, prog->d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        if (flag != 0xffffffffu)
+            return Status::err(EON_E_ARG, "lookup " + std::to_string(flag) + " (auxiliary column " +
+                                              std::to_string(prog->aux[flag]) +
+                                              "): a denominator alpha - fold(elements, beta) is zero on some row; "
+                                              "the permutation trace is not valid");
+        return Status::ok();
+    }();
+    return finish(ctx, s);
 }
 
 }  // extern "C"

@@ -42,6 +42,15 @@ int guarded(eon_kzg_pcs* h, F&& f) {
 
 void copy_out(const eon_host::Proof& p, eon_proof* out);
 void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out);
+void copy_out_lk(const eon_host::Proof& p, eon_proof_lk* out);
+
+void check_lk_arrays(const eon_air_program* prog, bool has_pp, const eon_proof_lk* out) {
+    if (has_pp && (!out->pp.preprocessed_commit || !out->pp.preprocessed_opened || !out->pp.preprocessed_witnesses))
+        throw eon_host::Error(EON_E_ARG, "null preprocessed output arrays");
+    if (eon_air_program_permutation_width(prog) > 0 &&
+        (!out->permutation_commit || !out->permutation_opened || !out->permutation_witnesses))
+        throw eon_host::Error(EON_E_ARG, "null permutation output arrays");
+}
 
 bool proof_arrays_ok(const eon_proof* out) {
     return out->trace_commit && out->quotient_commit && out->trace_opened && out->trace_witnesses &&
@@ -52,7 +61,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 4; }
+uint32_t eon_prove_abi_version(void) { return 5; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -263,6 +272,57 @@ int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
     });
 }
 
+int eon_prove_air_lk(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                     const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp, const eon_fr* pre_trace,
+                     const eon_fr* challenges, uint32_t n_challenges, const eon_fr* alpha, const eon_fr* zeta,
+                     eon_proof_lk* out) {
+    if (!pcs || !pcs->pcs || !prog || !trace || !alpha || !zeta || !out || (n_public && !publics) ||
+        (n_challenges && !challenges))
+        return EON_E_ARG;
+    if (!proof_arrays_ok(&out->pp.base)) return EON_E_ARG;
+    return guarded(pcs, [&] {
+        using namespace eon_host;
+        check_lk_arrays(prog, pp != nullptr, out);
+        if (n_challenges != eon_air_program_num_challenges(prog))
+            throw Error(EON_E_SHAPE, "challenge count differs from the program's");
+        AirRef a;
+        a.prog = prog;
+        a.publics = publics;
+        a.n_public = n_public;
+        LookupInputs lk;
+        lk.pre_trace = pre_trace;
+        lk.challenges = challenges;
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
+                        pp ? pp->pp.get() : nullptr, &lk);
+        copy_out_lk(p, out);
+    });
+}
+
+int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                        const eon_fr* publics, uint32_t n_public, const eon_preprocessed* pp,
+                        const eon_fr* pre_trace, eon_challenger* challenger, eon_proof_lk* out,
+                        eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out) {
+    if (!pcs || !pcs->pcs || !prog || !trace || !challenger || !out || (n_public && !publics)) return EON_E_ARG;
+    if (!proof_arrays_ok(&out->pp.base)) return EON_E_ARG;
+    return guarded(pcs, [&] {
+        using namespace eon_host;
+        check_lk_arrays(prog, pp != nullptr, out);
+        AirRef a;
+        a.prog = prog;
+        a.publics = publics;
+        a.n_public = n_public;
+        LookupInputs lk;
+        lk.pre_trace = pre_trace;
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch,
+                        pp ? pp->pp.get() : nullptr, &lk);
+        copy_out_lk(p, out);
+        if (challenges_out)
+            for (size_t i = 0; i < p.perm_challenges.size(); i++) challenges_out[i] = p.perm_challenges[i].abi();
+        if (alpha_out) *alpha_out = p.alpha.abi();
+        if (zeta_out) *zeta_out = p.zeta.abi();
+    });
+}
+
 int eon_prove_p2air_fs(eon_kzg_pcs* pcs, const eon_p2air* air, const eon_fr* trace, uint64_t height,
                        eon_challenger* challenger, uint32_t max_constraint_degree,
                        const eon_collective* shard, eon_proof* out, eon_fr* alpha_out, eon_fr* zeta_out) {
@@ -308,6 +368,17 @@ void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out) {
     for (int k = 0; k < 2; k++) {
         std::memcpy(out->preprocessed_opened + k * w, p.pre_opened[k].data(), w * sizeof(eon_fr));
         std::memcpy(out->preprocessed_witnesses + k * w, p.pre_witnesses[k].data(), w * sizeof(eon_g1_affine));
+    }
+}
+
+void copy_out_lk(const eon_host::Proof& p, eon_proof_lk* out) {
+    copy_out_pp(p, &out->pp);
+    const size_t w = p.perm_commit.size();
+    if (!w) return;
+    std::memcpy(out->permutation_commit, p.perm_commit.data(), w * sizeof(eon_g1_affine));
+    for (int k = 0; k < 2; k++) {
+        std::memcpy(out->permutation_opened + k * w, p.perm_opened[k].data(), w * sizeof(eon_fr));
+        std::memcpy(out->permutation_witnesses + k * w, p.perm_witnesses[k].data(), w * sizeof(eon_g1_affine));
     }
 }
 

@@ -3,7 +3,9 @@
 // quotient_values (328-342) -> commit_quotient (371-372) -> open at [zeta, zeta h] and [zeta] per
 // chunk (416-442).  With preprocessed columns (setup_preprocessed, preprocessed.rs:47-94) their
 // commitment is observed after the trace's (203-205), their evaluations on the quotient domain are
-// read by the constraints (321-322) and they are opened last, at [zeta, zeta h] (431).
+// read by the constraints (321-322) and they are opened last, at [zeta, zeta h] (431).  With lookups
+// the permutation challenges are sampled after the public values (214-216), the permutation trace is
+// generated, committed and observed (238-273) before alpha, and opened right after the trace (427-437).
 //
 // Lane sharding: the vectorized AIR evaluates its lanes one after another
 // (poseidon2-air/src/vectorized.rs:259-274), so lane v owns columns [164 v, 164 v + 164) and
@@ -82,7 +84,7 @@ std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_
 
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha_in,
             const Fr& zeta_in, uint32_t max_constraint_degree, const eon_collective* shard,
-            DuplexChallenger* challenger, const Preprocessed* pp) {
+            DuplexChallenger* challenger, const Preprocessed* pp, const LookupInputs* lookups) {
     eon_ctx* ctx = pcs.ctx();
     using clock = std::chrono::steady_clock;
     auto tick = [&] {
@@ -121,6 +123,15 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
             throw Error(EON_E_SHAPE, "preprocessed width " + std::to_string(pp->width) +
                                          " differs from the AIR's " + std::to_string(pre_width));
     }
+    // lookups (prover.rs:90-95): one running-sum column and two challenges each
+    const uint32_t perm_width = air.prog ? eon_air_program_permutation_width(air.prog) : 0;
+    const uint32_t n_challenges = air.prog ? eon_air_program_num_challenges(air.prog) : 0;
+    if (perm_width > 0 && !lookups)
+        throw Error(EON_E_ARG, "the program has lookups (permutation columns): prove it with eon_prove_air_lk");
+    if (perm_width > 0 && eon_air_program_num_lookups(air.prog) != perm_width)
+        throw Error(EON_E_ARG, "the program has permutation columns but no lookup description");
+    if (perm_width > 0 && !challenger && !lookups->challenges)
+        throw Error(EON_E_ARG, "null permutation challenges");
     // get_log_quotient_degree (prover.rs:150-157): the program's own constraint degrees
     const uint32_t log_qd =
         air.prog ? eon_air_program_log_quotient_degree(air.prog, 0) : log_quotient_degree(max_constraint_degree);
@@ -136,7 +147,12 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     std::vector<MatrixProverData> trace_data;
     const Domain quotient_domain = trace_domain.create_disjoint_domain(1ull << (log_n + log_qd));
     const uint64_t q_rows = quotient_domain.size();
-    DeviceMatrix lde, pre_lde;
+    DeviceMatrix lde, pre_lde, perm_lde;
+    std::vector<std::vector<eon_g1_affine>> perm_commit;
+    std::vector<MatrixProverData> perm_data;
+    std::vector<Fr> perm_challenges(n_challenges);
+    if (perm_width > 0 && !challenger)
+        for (uint32_t i = 0; i < n_challenges; i++) perm_challenges[i] = Fr::from_abi(lookups->challenges[i]);
     clock::time_point t1, t2;
     {
         std::vector<std::pair<Domain, DeviceMatrix>> ev;
@@ -171,7 +187,10 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
             if (pp) challenger->observe_g1(pp->commitment.data(), pp->commitment.size());  // prover.rs:203-205
             for (uint32_t i = 0; i < air.n_public; i++)  // observe_slice(public_values), prover.rs:208
                 challenger->observe(Fr::from_abi(air.publics[i]));
-            alpha = challenger->sample();  // no lookups
+            if (perm_width > 0)  // prover.rs:214-216; alpha follows the permutation commitment
+                for (uint32_t i = 0; i < n_challenges; i++) perm_challenges[i] = challenger->sample();
+            else
+                alpha = challenger->sample();
         });
     }
     // the trace LDE (prover.rs:315) while the host thread runs the transcript up to alpha
@@ -184,6 +203,25 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         throw;
     }
     if (fs_thread.joinable()) fs_thread.join();
+    if (perm_width > 0) {
+        // generate_permutation (prover.rs:238-245), commit on the trace domain (:270), observe
+        // (:273), alpha (:300), then the permutation trace on the quotient domain (:317-319)
+        DeviceMatrix perm = DeviceMatrix::alloc(height, perm_width);
+        std::vector<eon_fr> ch(n_challenges);
+        for (uint32_t i = 0; i < n_challenges; i++) ch[i] = perm_challenges[i].abi();
+        check(ctx,
+              eon_lookup_permutation_dev(ctx, air.prog, trace, lookups->pre_trace, height, air.publics, air.n_public,
+                                         ch.data(), n_challenges, perm.mutable_data()),
+              "generate_permutation");
+        std::vector<std::pair<Domain, DeviceMatrix>> ev;
+        ev.emplace_back(trace_domain, std::move(perm));
+        pcs.commit(std::move(ev), perm_commit, perm_data);
+        if (challenger) {
+            challenger->observe_g1(perm_commit[0].data(), perm_commit[0].size());
+            alpha = challenger->sample();
+        }
+        perm_lde = pcs.get_evaluations_on_domain(perm_data, 0, quotient_domain);
+    }
     DeviceMatrix qv = DeviceMatrix::alloc(q_rows, 1);
     {
         t2 = tick();
@@ -191,7 +229,15 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         if (air.p2)
             check(ctx, eon_p2air_quotient_values_dev(ctx, air.p2, lde.data(), log_n, log_qd, &a, qv.mutable_data()),
                   "quotient_values");
-        else if (pp)
+        else if (perm_width > 0) {
+            std::vector<eon_fr> ch(n_challenges);
+            for (uint32_t i = 0; i < n_challenges; i++) ch[i] = perm_challenges[i].abi();
+            check(ctx,
+                  eon_quotient_values_lk_dev(ctx, air.prog, lde.data(), pp ? pre_lde.data() : nullptr, perm_lde.data(),
+                                             log_n, log_qd, &a, air.publics, air.n_public, ch.data(), n_challenges,
+                                             qv.mutable_data()),
+                  "quotient_values");
+        } else if (pp)
             check(ctx,
                   eon_quotient_values_pp_dev(ctx, air.prog, lde.data(), pre_lde.data(), log_n, log_qd, &a,
                                              air.publics, air.n_public, qv.mutable_data()),
@@ -205,6 +251,7 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     check(ctx, eon_ctx_synchronize(ctx), "quotient_values");
     lde = DeviceMatrix();  // back to the buffer cache before the opening
     pre_lde = DeviceMatrix();
+    perm_lde = DeviceMatrix();
     auto t3 = tick();
     if (shard) {
         DeviceBuffer parts(sizeof(eon_fr) * q_rows * world);
@@ -250,15 +297,27 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     proof.zeta = zeta;
     auto t4 = tick();
     const Fr zeta_next = trace_domain.next_point(zeta);  // prover.rs:416-419
-    std::vector<OpenRound> rounds(2);
+    // the rounds in the reference's order (prover.rs:426-439): trace, permutation, quotient chunks,
+    // preprocessed
+    std::vector<OpenRound> rounds(1);
     rounds[0].data = &trace_data;
     rounds[0].points = {{zeta, zeta_next}};
-    rounds[1].data = &quotient_data;
-    rounds[1].points.assign(quotient_data.size(), std::vector<Fr>{zeta});
-    if (pp) {  // round3 (prover.rs:431): after the quotient chunks
+    size_t i_perm = 0, i_pre = 0;
+    if (perm_width > 0) {
+        i_perm = rounds.size();
         rounds.emplace_back();
-        rounds[2].data = &pp->data;
-        rounds[2].points = {{zeta, zeta_next}};
+        rounds.back().data = &perm_data;
+        rounds.back().points = {{zeta, zeta_next}};
+    }
+    const size_t i_quot = rounds.size();
+    rounds.emplace_back();
+    rounds.back().data = &quotient_data;
+    rounds.back().points.assign(quotient_data.size(), std::vector<Fr>{zeta});
+    if (pp) {  // round3 (prover.rs:431): after the quotient chunks
+        i_pre = rounds.size();
+        rounds.emplace_back();
+        rounds.back().data = &pp->data;
+        rounds.back().points = {{zeta, zeta_next}};
     }
     // the opening bases are the same on every rank: sharded over the process group
     // (eon_ctx_set_collective)
@@ -281,16 +340,16 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     proof.quotient_witnesses.resize(num_chunks);
     if (!shard) {
         for (uint32_t c = 0; c < num_chunks; c++) {
-            proof.quotient_opened[c] = opened[1].values[c][0][0];
-            proof.quotient_witnesses[c] = opened[1].witnesses[c][0][0];
+            proof.quotient_opened[c] = opened[i_quot].values[c][0][0];
+            proof.quotient_witnesses[c] = opened[i_quot].witnesses[c][0][0];
         }
     } else {
         // every rank's chunk openings to every rank: value (4 u64) | witness (8 u64) per slot
         constexpr uint32_t QREC = 12;
         std::vector<uint64_t> rec((uint64_t)chunk_slots * QREC, 0);
         for (size_t i = 0; i < my_chunks.size(); i++) {
-            std::memcpy(&rec[i * QREC], &opened[1].values[i][0][0], 32);
-            std::memcpy(&rec[i * QREC + 4], &opened[1].witnesses[i][0][0], 64);
+            std::memcpy(&rec[i * QREC], &opened[i_quot].values[i][0][0], 32);
+            std::memcpy(&rec[i * QREC + 4], &opened[i_quot].witnesses[i][0][0], 64);
         }
         const uint64_t bytes = rec.size() * sizeof(uint64_t);
         DeviceBuffer send(bytes), recv(bytes * world);
@@ -308,8 +367,16 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     if (pp) {
         proof.pre_commit = pp->commitment;
         for (int p = 0; p < 2; p++) {
-            proof.pre_opened[p] = opened[2].values[0][p];
-            proof.pre_witnesses[p] = opened[2].witnesses[0][p];
+            proof.pre_opened[p] = opened[i_pre].values[0][p];
+            proof.pre_witnesses[p] = opened[i_pre].witnesses[0][p];
+        }
+    }
+    if (perm_width > 0) {
+        proof.perm_challenges = perm_challenges;
+        proof.perm_commit = perm_commit[0];
+        for (int p = 0; p < 2; p++) {
+            proof.perm_opened[p] = opened[i_perm].values[0][p];
+            proof.perm_witnesses[p] = opened[i_perm].witnesses[0][p];
         }
     }
     const Opened& tr = opened[0];

@@ -1,9 +1,10 @@
 // prove_with_preprocessed (eon-uni-stark/src/prover.rs:28-512) over KzgPcs, as a C++ driver above
 // eon.h, for the Poseidon2-AIR (fused quotient kernel) or any AIR given as a constraint program
 // with public values and, optionally, preprocessed columns (the Some(preprocessed) branch:
-// setup_preprocessed, eon-uni-stark/src/preprocessed.rs:47-94): no lookups, ZK off (KzgPcs::ZK =
-// false, kzg/src/pcs.rs:216), Challenge = Fr; alpha and zeta are inputs or sampled from a
-// DuplexChallenger.
+// setup_preprocessed, eon-uni-stark/src/preprocessed.rs:47-94) and local LogUp lookups (the
+// Some(permutation) branch, prover.rs:210-278, 317-319, 427-437): ZK off (KzgPcs::ZK = false,
+// kzg/src/pcs.rs:216), Challenge = Fr; the challenges are inputs or sampled from a DuplexChallenger
+// (SURVEY.md 8(f) N2).
 #pragma once
 #include "eon_prove.h"
 #include "pcs.h"
@@ -29,6 +30,20 @@ struct Proof {
     std::vector<eon_g1_affine> pre_commit;        // [Wp]
     std::vector<eon_fr> pre_opened[2];            // at zeta, zeta * h: [Wp] each
     std::vector<eon_g1_affine> pre_witnesses[2];  // [Wp] each
+    // with lookups (proof.rs commitments.permutation, opened_values.permutation_local / _next)
+    std::vector<Fr> perm_challenges;               // [2 Wq], the challenges used
+    std::vector<eon_g1_affine> perm_commit;        // [Wq]
+    std::vector<eon_fr> perm_opened[2];            // at zeta, zeta * h: [Wq] each
+    std::vector<eon_g1_affine> perm_witnesses[2];  // [Wq] each
+};
+
+// What a program with lookups needs beyond the plain prove: the preprocessed trace on the trace
+// domain (device, height x Wp; what air.preprocessed_trace() returns next to the committed data,
+// prover.rs:220-224), required when a lookup tuple reads a preprocessed column, and the permutation
+// challenges when they are given rather than sampled (host, 2 Wq).
+struct LookupInputs {
+    const eon_fr* pre_trace = nullptr;
+    const eon_fr* challenges = nullptr;
 };
 
 // PreprocessedProverData (preprocessed.rs:12-24): the preprocessed trace committed once per
@@ -61,9 +76,15 @@ struct AirRef {
 // max_constraint_degree is the Poseidon2-AIR's (3); a program carries its own.  `preprocessed`
 // (programs only, no sharding) is required exactly when the program has preprocessed columns: it is
 // observed after the trace commitment (prover.rs:196-208), extended to the quotient domain for the
-// constraints (:321-322) and opened at {zeta, zeta h} in a third round (:426-439).
+// constraints (:321-322) and opened at {zeta, zeta h} in a third round (:426-439).  `lookups`
+// (programs only, no sharding) is required exactly when the program has permutation columns: the
+// 2 Wq challenges are sampled after the public values (:214-216), generate_permutation runs on the
+// device (:238-245), its trace is committed on the trace domain and observed (:270-273) before
+// alpha (:300), extended next to the trace (:317-319) and opened at {zeta, zeta h} in the round
+// after the trace's (:427-437).
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha,
             const Fr& zeta, uint32_t max_constraint_degree, const eon_collective* shard,
-            DuplexChallenger* challenger = nullptr, const Preprocessed* preprocessed = nullptr);
+            DuplexChallenger* challenger = nullptr, const Preprocessed* preprocessed = nullptr,
+            const LookupInputs* lookups = nullptr);
 
 }  // namespace eon_host

@@ -47,6 +47,11 @@ class eon_proof_pp(ctypes.Structure):
                 ("preprocessed_witnesses", _P)]
 
 
+class eon_proof_lk(ctypes.Structure):
+    _fields_ = [("pp", eon_proof_pp), ("permutation_commit", _P), ("permutation_opened", _P),
+                ("permutation_witnesses", _P)]
+
+
 # name -> (restype, argtypes): every entry point of include/eon_prove.h
 SIGNATURES = {
     "eon_prove_abi_version": (_U32, []),
@@ -80,6 +85,8 @@ SIGNATURES = {
     "eon_preprocessed_commitment": (_INT, [_P, _P]),
     "eon_prove_air_pp": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, ctypes.POINTER(eon_proof_pp)]),
     "eon_prove_air_pp_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_pp), _P, _P]),
+    "eon_prove_air_lk": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_lk)]),
+    "eon_prove_air_lk_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, ctypes.POINTER(eon_proof_lk), _P, _P, _P]),
 }
 
 _plib = None
@@ -342,14 +349,20 @@ def setup_preprocessed(pcs: NativeKzgPcs, pre_trace) -> Preprocessed:
 
 def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | None,
                  max_constraint_degree: int = 3, collective=None, challenger: Challenger | None = None,
-                 public_values=(), preprocessed: Preprocessed | None = None) -> Proof:
+                 public_values=(), preprocessed: Preprocessed | None = None, permutation_challenges=None,
+                 preprocessed_trace=None) -> Proof:
     """prover.prove through the C++ driver.  `air` is a Poseidon2Air (fused quotient kernel) or an
     air.AirProgram (any AIR, with `public_values`: canonical ints).  `trace`: (N, width, 4) device
     tensor; with a collective (world > 1, Poseidon2 only) `air`/`trace` are this rank's lanes and
     the proof is the full one.  With `challenger` (eon_prove_*_fs) alpha and zeta are sampled from
     the transcript and returned in proof.alpha / proof.zeta (canonical ints); the arguments are
     ignored.  With `preprocessed` (setup_preprocessed; generic AIRs only) the proof carries its
-    commitment and a third Opened entry, the preprocessed columns at zeta and zeta * h."""
+    commitment and a third Opened entry, the preprocessed columns at zeta and zeta * h.  An
+    AirProgram with lookups goes through eon_prove_air_lk[_fs]: `permutation_challenges` (canonical
+    ints) are given next to alpha and zeta, or sampled with `challenger`; `preprocessed_trace` is
+    the (N, Wp, 4) preprocessed trace itself when a lookup reads it.  The proof then carries
+    permutation_commit and permutation_challenges, and its `opened` list has the permutation
+    columns second (the reference's rounds: trace, permutation, quotient chunks, preprocessed)."""
     from .air import AirProgram, _publics_limbs
 
     generic = isinstance(air, AirProgram)
@@ -373,6 +386,20 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         pw = np.zeros((2, wp, 8), np.uint64)
         out_pp = eon_proof_pp(out, _p(pc), _p(po), _p(pw))
         out = out_pp.base  # a view: the driver's degree_bits and stage_ms land here
+    lookups = generic and air.permutation_width > 0
+    if lookups:
+        if collective is not None:
+            raise ValueError("lookups are not lane-sharded")
+        wq = air.permutation_width
+        mc = np.zeros((wq, 8), np.uint64)
+        mo = np.zeros((2, wq, 4), np.uint64)
+        mw = np.zeros((2, wq, 8), np.uint64)
+        if preprocessed is None:
+            out_pp = eon_proof_pp(out, None, None, None)
+        out_lk = eon_proof_lk(out_pp, _p(mc), _p(mo), _p(mw))
+        out = out_lk.pp.base
+    elif permutation_challenges is not None or preprocessed_trace is not None:
+        raise ValueError("permutation_challenges / preprocessed_trace need an AirProgram with lookups")
     t = trace.contiguous()
     import torch
 
@@ -384,7 +411,26 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     if not generic and npub:
         raise ValueError("the Poseidon2-AIR has no public values")
     tp = ctypes.c_void_p(t.data_ptr())
-    if challenger is None:
+    if lookups:
+        pt = preprocessed_trace.contiguous() if preprocessed_trace is not None else None
+        ptp = ctypes.c_void_p(pt.data_ptr()) if pt is not None else None
+        pph = preprocessed.handle if preprocessed is not None else None
+        if challenger is None:
+            a, z = fr_to_abi(alpha), fr_to_abi(zeta)
+            chal = [int(c) for c in (permutation_challenges or ())]
+            ch = _publics_limbs(chal)
+            pcs.check(pcs.lib.eon_prove_air_lk(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, pph, ptp,
+                                               _p(ch), len(chal), ctypes.byref(a), ctypes.byref(z),
+                                               ctypes.byref(out_lk)))
+        else:
+            a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+            c_out = np.zeros((air.num_challenges, 4), np.uint64)
+            pcs.check(pcs.lib.eon_prove_air_lk_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, pph, ptp,
+                                                  challenger.handle, ctypes.byref(out_lk), _p(c_out), _p(a_out),
+                                                  _p(z_out)))
+            unm = lambda v: fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v)))  # noqa: E731
+            alpha, zeta, chal = unm(a_out), unm(z_out), [unm(c) for c in c_out]
+    elif challenger is None:
         a, z = fr_to_abi(alpha), fr_to_abi(zeta)
         if preprocessed is not None:
             pcs.check(pcs.lib.eon_prove_air_pp(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
@@ -420,7 +466,9 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         timings.pop("exchange partial quotients")
         timings.pop("assemble columns")
     opened = [opened_trace, opened_quot]
-    if preprocessed is None:
-        return Proof([tc], [qc[c:c + 1] for c in range(chunks)], opened, out.degree_bits, timings, alpha, zeta)
-    opened.append(Opened(values=[[po[0], po[1]]], witnesses=[[pw[0], pw[1]]]))
-    return Proof([tc], [qc[c:c + 1] for c in range(chunks)], opened, out.degree_bits, timings, alpha, zeta, [pc])
+    if lookups:  # the permutation round comes before the quotient's (prover.rs:426-439)
+        opened.insert(1, Opened(values=[[mo[0], mo[1]]], witnesses=[[mw[0], mw[1]]]))
+    if preprocessed is not None:
+        opened.append(Opened(values=[[po[0], po[1]]], witnesses=[[pw[0], pw[1]]]))
+    return Proof([tc], [qc[c:c + 1] for c in range(chunks)], opened, out.degree_bits, timings, alpha, zeta,
+                 [pc] if preprocessed is not None else None, [mc] if lookups else None, chal if lookups else None)

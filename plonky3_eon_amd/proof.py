@@ -26,6 +26,11 @@ class Proof:
     zeta: int | None = None
     # with preprocessed columns: the setup's commitment [(Wp, 8)]; their openings are opened[2]
     preprocessed_commit: object = None
+    # with lookups: the permutation trace's commitment [(Wq, 8)] and the 2 Wq challenges used
+    # (canonical ints); `opened` follows the reference's rounds (prover.rs:426-439): trace,
+    # permutation, quotient chunks, preprocessed
+    permutation_commit: object = None
+    permutation_challenges: list | None = None
 
 
 def log_quotient_degree(max_constraint_degree: int) -> int:

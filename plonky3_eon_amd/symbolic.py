@@ -12,6 +12,8 @@ Mirrors eon-uni-stark's symbolic layer so an AIR written against the reference's
 * ``FilteredAirBuilder``                 eon-air/src/filtered_builder.rs:25-70 (cond * x)
 * ``assert_eq / assert_one / assert_bool / when*``   eon-air/src/builder.rs:109-182
 * ``get_max_constraint_degree`` / ``get_log_quotient_degree``   symbolic_builder.rs:15-69
+* ``Lookup`` / ``Kind`` / ``Direction`` / ``register_lookup``   lookup/src/lookup_traits.rs:150-248
+* ``LogUpGadget``                        lookup/src/logup.rs:62-377 (local lookups)
 
 ``serialize`` flattens the constraint DAG into the ``eon_sym_node`` array that
 ``eon_air_program_create`` (include/eon.h) compiles into a device program -- the same array a Rust
@@ -347,16 +349,186 @@ def air_width(air) -> int:
     return int(w() if callable(w) else w)
 
 
-def get_symbolic_constraints(air, preprocessed_width: int = 0, num_public_values: int | None = None,
-                             permutation_width: int = 0, num_permutation_challenges: int = 0):
-    """symbolic_builder.rs:72-115 (no lookups: AirLookupHandler::eval is Air::eval,
-    lookup/src/lookup_traits.rs:257-269)."""
+class Kind:
+    """lookup_traits.rs:150-159.  ``Kind.Local`` or ``Kind.Global(name)``; global lookups span
+    several AIRs and are refused here (see ``LogUpGadget.eval_lookups``)."""
+
+    Local = ("local", None)
+
+    @staticmethod
+    def Global(name: str):
+        return ("global", name)
+
+
+class Direction:
+    """lookup_traits.rs:161-178: Send negates the multiplicity, Receive keeps it."""
+
+    SEND = "send"
+    RECEIVE = "receive"
+
+    @staticmethod
+    def multiplicity(direction, mult):
+        mult = SymbolicExpression.lift(mult)
+        if direction == Direction.SEND:
+            return -mult
+        if direction == Direction.RECEIVE:
+            return mult
+        raise ValueError(f"unknown direction {direction!r}")
+
+
+@dataclass
+class Lookup:
+    """lookup_traits.rs:186-220: element tuples, one multiplicity per tuple, the auxiliary columns."""
+
+    kind: tuple
+    element_exprs: list
+    multiplicities_exprs: list
+    columns: list
+
+
+def register_lookup(air, kind, lookup_inputs) -> Lookup:
+    """AirLookupHandler::register_lookup (lookup_traits.rs:229-248): `lookup_inputs` is a list of
+    (elements, multiplicity, direction); the columns come from the AIR's add_lookup_columns()."""
+    elements = [[SymbolicExpression.lift(e) for e in elems] for elems, _, _ in lookup_inputs]
+    mults = [Direction.multiplicity(d, m) for _, m, d in lookup_inputs]
+    return Lookup(kind, elements, mults, list(air.add_lookup_columns()))
+
+
+class LogUpGadget:
+    """lookup/src/logup.rs: one running-sum column s per lookup, s[0] = 0 and
+    s[i+1] = s[i] + sum_t m_t / (alpha - fold(elements_t, beta))."""
+
+    num_aux_cols = 1
+    num_challenges = 2
+
+    def combine_elements(self, elements, alpha, beta):
+        """logup.rs:70-92: alpha - fold(0, acc -> elt + acc * beta) per tuple."""
+        out = []
+        for elts in elements:
+            acc = SymbolicExpression.constant(0)
+            for e in elts:
+                acc = SymbolicExpression.lift(e) + acc * beta
+            out.append(SymbolicExpression.lift(alpha) - acc)
+        return out
+
+    def compute_combined_sum_terms(self, elements, multiplicities, alpha, beta, terms=None):
+        """logup.rs:97-142 -> (numerator, common denominator).  `terms`: the per-tuple denominators
+        when they were built already (they are then shared, not rebuilt)."""
+        one = SymbolicExpression.constant(1)
+        if not elements:
+            return SymbolicExpression.constant(0), one
+        n = len(elements)
+        if terms is None:
+            terms = self.combine_elements(elements, alpha, beta)
+        pref = [one]
+        for t in terms:
+            pref.append(pref[-1] * t)
+        suff = [one] * (n + 1)
+        for i in range(n - 1, -1, -1):
+            suff[i] = suff[i + 1] * terms[i]
+        numerator = SymbolicExpression.constant(0)
+        for i in range(n):
+            numerator = numerator + SymbolicExpression.lift(multiplicities[i]) * pref[i] * suff[i + 1]
+        return numerator, pref[n]
+
+    def denominators(self, lookup: Lookup, challenges):
+        """The per-tuple denominators of one lookup over the challenge variables: alpha =
+        challenges[2c], beta = challenges[2c + 1] for auxiliary column c (logup.rs:206-209)."""
+        if len(lookup.element_exprs) != len(lookup.multiplicities_exprs):
+            raise ValueError("Mismatched lengths: elements and multiplicities must have same length")
+        if len(lookup.columns) != self.num_aux_cols:
+            raise ValueError("There is exactly one auxiliary column for LogUp")
+        c = lookup.columns[0]
+        if len(challenges) < self.num_challenges * (c + 1):
+            raise ValueError("Insufficient permutation challenges")
+        alpha = SymbolicExpression.lift(challenges[self.num_challenges * c])
+        beta = SymbolicExpression.lift(challenges[self.num_challenges * c + 1])
+        return self.combine_elements(lookup.element_exprs, alpha, beta)
+
+    def eval_local_lookup(self, builder, lookup: Lookup, terms=None):
+        """eval_update for Kind::Local (logup.rs:154-263): when_first_row s_local, then
+        (s_next - s_local) * denominator - numerator on every row."""
+        if lookup.kind[0] != "local":
+            raise NotImplementedError("Global lookups are not supported in local evaluation")
+        challenges = builder.permutation_randomness()
+        if terms is None:
+            terms = self.denominators(lookup, challenges)
+        c = lookup.columns[0]
+        perm = builder.permutation()
+        if len(perm[0]) <= c:
+            raise ValueError("Permutation trace has insufficient width")
+        s_local, s_next = SymbolicExpression.lift(perm[0][c]), SymbolicExpression.lift(perm[1][c])
+        builder.when_first_row().assert_zero(s_local)
+        numerator, denominator = self.compute_combined_sum_terms(lookup.element_exprs, lookup.multiplicities_exprs,
+                                                                 None, None, terms)
+        builder.assert_zero((s_next - s_local) * denominator - numerator)
+
+    @staticmethod
+    def check_local(lookups):
+        """Local lookups only: a global lookup needs the other AIRs' cumulated values, and the
+        reference's own single-AIR verifier passes no lookup_data (eon-uni-stark/src/verifier.rs:498),
+        so it could not verify there either."""
+        for i, lk in enumerate(lookups):
+            if lk.kind[0] != "local":
+                raise NotImplementedError(f"lookup {i} is Kind.Global({lk.kind[1]!r}): only local lookups are "
+                                          "supported (a single-AIR proof carries no lookup_data to verify a "
+                                          "global one against)")
+
+    def eval_lookups(self, builder, lookups, terms=None):
+        """LookupGadget::eval_lookups (lookup_traits.rs:85-122), local lookups only."""
+        self.check_local(lookups)
+        for i, lk in enumerate(lookups):
+            self.eval_local_lookup(builder, lk, None if terms is None else terms[i])
+
+    def constraint_degree(self, lookup: Lookup) -> int:
+        """logup.rs:348-377."""
+        assert len(lookup.multiplicities_exprs) == len(lookup.element_exprs)
+        degs = [max((SymbolicExpression.lift(e).degree_multiple for e in elems), default=0)
+                for elems in lookup.element_exprs]
+        deg_sum = sum(degs)
+        deg_num = max((SymbolicExpression.lift(m).degree_multiple + deg_sum - d
+                       for m, d in zip(lookup.multiplicities_exprs, degs)), default=0)
+        return max(1 + deg_sum, deg_num)
+
+
+def air_lookups(air) -> list:
+    """AirLookupHandler::get_lookups: an AIR declares lookups by having get_lookups()."""
+    return list(air.get_lookups()) if hasattr(air, "get_lookups") else []
+
+
+def get_symbolic_constraints_and_lookups(air, preprocessed_width: int = 0, num_public_values: int | None = None,
+                                         permutation_width: int = 0, num_permutation_challenges: int = 0):
+    """get_symbolic_constraints plus what generate_permutation needs: (constraints, lookups, terms),
+    terms[l] = [(denominator, multiplicity)] of lookup l.  The denominators are the very expression
+    objects the constraints use, so one serialised DAG holds both as shared nodes."""
     if num_public_values is None:
         num_public_values = air.num_public_values()
+    lookups = air_lookups(air)
+    gadget = LogUpGadget()
+    if lookups:  # prover.rs:90-95
+        permutation_width = len(lookups) * gadget.num_aux_cols
+        num_permutation_challenges = len(lookups) * gadget.num_challenges
     b = SymbolicAirBuilder(preprocessed_width, air_width(air), num_public_values, permutation_width,
                            num_permutation_challenges)
-    air.eval(b)
-    return b.constraints
+    air.eval(b)  # AirLookupHandler::eval (lookup_traits.rs:257-269): the AIR first, then the lookups
+    terms = []
+    if lookups:
+        gadget.check_local(lookups)
+        dens =[gadget.denominators(lk, b.permutation_randomness()) for lk in lookups]
+        gadget.eval_lookups(b, lookups, dens)
+        terms = [list(zip(d, [SymbolicExpression.lift(m) for m in lk.multiplicities_exprs]))
+                 for d, lk in zip(dens, lookups)]
+    return b.constraints, lookups, terms
+
+
+def get_symbolic_constraints(air, preprocessed_width: int = 0, num_public_values: int | None = None,
+                             permutation_width: int = 0, num_permutation_challenges: int = 0):
+    """symbolic_builder.rs:72-115.  Without lookups AirLookupHandler::eval is Air::eval
+    (lookup/src/lookup_traits.rs:257-269); with them (the AIR has get_lookups()) the LogUp
+    constraints follow the AIR's own, in list order, over len(lookups) permutation columns and
+    2 len(lookups) challenges."""
+    return get_symbolic_constraints_and_lookups(air, preprocessed_width, num_public_values, permutation_width,
+                                                num_permutation_challenges)[0]
 
 
 def get_max_constraint_degree(air, preprocessed_width: int = 0, num_public_values: int | None = None) -> int:
