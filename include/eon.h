@@ -152,13 +152,75 @@ int eon_diag_clock_probe(eon_ctx* ctx, uint32_t launches, uint32_t iters, eon_cl
  * bounds (half of them at the maximum limb); mismatches[0..2] = mismatching mul / sqr / sum2
  * cases. */
 int eon_diag_prod_asm_check(eon_ctx* ctx, uint32_t n, uint32_t seed, uint32_t mismatches[3]);
+/* The same for the in-place forms the piece sums' hot loop uses (mul29_asm_ip: a = a b;
+ * mul29_sum2_asm_ip: c = a b + c d; tied read-write operands, another register arrangement than
+ * the out-of-place statements): operands drawn as above, the overwritten operand copied first,
+ * results compared bit for bit with the column-block mul29 / mul29_sum2.  mismatches[0..1] =
+ * mismatching mul / sum2 cases. */
+int eon_diag_prod_asm_ip_check(eon_ctx* ctx, uint32_t n, uint32_t seed, uint32_t mismatches[2]);
+/* The stages of the MSM digit pipeline on their own (tests; host pointers, synchronous, scratch
+ * from the context's pool).
+ * eon_diag_radix_sort_pairs: the stable LSD radix sort of the n pairs (keys[i], vals[i]) on key
+ *   bits [0, bits), bits <= 32, with the sort's own histogram kernel; key bits above `bits` do not
+ *   order and are kept.  n <= 2^24.
+ * eon_diag_exclusive_scan_u32: out[i] = in[0] + ... + in[i-1] modulo 2^32, n <= 2^24.
+ * eon_diag_scan_chunk_counts: the piece offsets of nb buckets given by their nb + 1 `start`s: the
+ *   exclusive sum (nb + 1 outputs) of count[b] = the 2^log_chunk-aligned runs the pairs
+ *   [start[b], start[b+1]) touch (0 if empty, count[nb] = 0); *max_out = the largest count if it
+ *   exceeds 1, else 0.  nb <= 2^24, log_chunk < 32. */
+int eon_diag_radix_sort_pairs(eon_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint64_t n, uint32_t bits,
+                              uint32_t* keys_out, uint32_t* vals_out);
+int eon_diag_exclusive_scan_u32(eon_ctx* ctx, const uint32_t* in, uint64_t n, uint32_t* out);
+int eon_diag_scan_chunk_counts(eon_ctx* ctx, const uint32_t* start, uint32_t nb, uint32_t log_chunk, uint32_t* out,
+                               uint32_t* max_out);
+/* What a prepared handle (eon_msm_g1_columns_prepare_dev) keeps of its column batches.  A batch
+ * covers columns [col0, col0 + cols) with window width c and `windows` digit windows per scalar;
+ * `ref_windows` is the window count of the bases' layout (a fixed-base reference is row *
+ * ref_windows + window).  Keys are (group << c) | (|digit| - 1) with `groups` groups (the batch's
+ * columns, or column x window without fixed-base tables), nb = groups * 2^(c-1) buckets, bucket
+ * (|digit| - 1) * groups + group.  The batch keeps `pairs` = rows * windows * cols sorted (key, value)
+ * pairs, of which the first n_pairs are nonzero digits in bucket order and the rest the zero-digit
+ * sentinel 0xFFFFFFFF; start[b] = the first pair of bucket >= b (nb + 1 entries) and piece_off = the
+ * piece offsets of `start` at log_chunk (nb + 1 entries, n_pieces = piece_off[nb]). */
+typedef struct {
+    uint64_t pairs;
+    uint32_t c;
+    uint32_t windows;
+    uint32_t ref_windows;
+    uint32_t groups;
+    uint32_t nb;
+    uint32_t log_chunk;
+    uint32_t cols;
+    uint32_t col0;
+    uint32_t n_pairs;
+    uint32_t n_pieces;
+} eon_msm_batch_info;
+/* The number of batches of `prepared` (0 for an empty matrix). */
+int eon_diag_msm_scalars_batches(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t* count);
+/* Batch k's layout into *info and copies of its kept arrays into the host buffers that are not
+ * NULL: keys / vals (info->pairs entries each), start / piece_off (info->nb + 1 entries each).
+ * Reads only; the handle is unchanged. */
+int eon_diag_msm_scalars_batch(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t k, eon_msm_batch_info* info,
+                               uint32_t* keys, uint32_t* vals, uint32_t* start, uint32_t* piece_off);
 
-/* ABI version; bumped on any signature or struct-layout change (6: the LogUp lookup entry points
- * eon_air_program_create_lk / eon_quotient_values_lk_dev / eon_lookup_permutation_dev, additive;
- * 5: preprocessed columns in the generic quotient, eon_air_program_create_pp / eon_quotient_values_pp_dev, additive; 4: the
- * verifier pairings and their eon_g2_affine / eon_fq12 types; 3: eon_collective's all_to_all
- * field).  Bindings must check it at load time: a binding built against an older layout would pass
- * a shorter eon_collective. */
+/* One single-column MSM over device scalars as eon_msm_g1_dev runs it -- digitising only the
+ * windows its largest scalar reaches (one more for the recoding's carry), which a handle made by
+ * eon_msm_g1_columns_prepare_dev never does -- that also keeps its one batch in *prepared, for
+ * eon_diag_msm_scalars_batch to read back: info->windows may then be below info->ref_windows while
+ * the fixed-base references stay row * ref_windows + window.  *out receives the MSM's point. */
+int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases, const eon_fr* scalars, uint64_t n,
+                                       eon_g1_affine* out, eon_msm_scalars** prepared);
+
+/* ABI version; bumped on any signature or struct-layout change.
+ *   7: the eon_diag_* stage diagnostics of the MSM digit pipeline and eon_msm_batch_info, additive;
+ *   6: the LogUp lookup entry points eon_air_program_create_lk / eon_quotient_values_lk_dev /
+ *      eon_lookup_permutation_dev, additive;
+ *   5: preprocessed columns in the generic quotient, eon_air_program_create_pp /
+ *      eon_quotient_values_pp_dev, additive;
+ *   4: the verifier pairings and their eon_g2_affine / eon_fq12 types;
+ *   3: eon_collective's all_to_all field.
+ * Bindings must check it at load time: a binding built against an older layout would pass a
+ * shorter eon_collective. */
 uint32_t eon_abi_version(void);
 
 /* ---- TwoAdicSubgroupDft<Fr> (dft/src/traits.rs:27-249) -----------------------------------

@@ -23,7 +23,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 6  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 7  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -74,6 +74,11 @@ class eon_clock_probe(ctypes.Structure):
                                               "ms_per_launch")]
 
 
+class eon_msm_batch_info(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_uint64)] + [(k, ctypes.c_uint32) for k in (
+        "c", "windows", "ref_windows", "groups", "nb", "log_chunk", "cols", "col0", "n_pairs", "n_pieces")]
+
+
 class eon_g1_affine(ctypes.Structure):
     _fields_ = [("x", ctypes.c_uint64 * 4), ("y", ctypes.c_uint64 * 4)]
 
@@ -97,6 +102,13 @@ SIGNATURES = {
     "eon_ctx_trim": (_INT, [_P]),
     "eon_diag_clock_probe": (_INT, [_P, _U32, _U32, _P]),
     "eon_diag_prod_asm_check": (_INT, [_P, _U32, _U32, _P]),
+    "eon_diag_prod_asm_ip_check": (_INT, [_P, _U32, _U32, _P]),
+    "eon_diag_radix_sort_pairs": (_INT, [_P, _P, _P, _U64, _U32, _P, _P]),
+    "eon_diag_exclusive_scan_u32": (_INT, [_P, _P, _U64, _P]),
+    "eon_diag_scan_chunk_counts": (_INT, [_P, _P, _U32, _U32, _P, _P]),
+    "eon_diag_msm_g1_prepare_active_dev": (_INT, [_P, _P, _P, _U64, _P, ctypes.POINTER(_P)]),
+    "eon_diag_msm_scalars_batches": (_INT, [_P, _P, _P]),
+    "eon_diag_msm_scalars_batch": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _P]),
     "eon_ctx_profile": (_INT, [_P, _INT]),
     "eon_ctx_profile_report": (_INT, [_P, ctypes.c_char_p, _U64]),
     "eon_ctx_set_serial": (_INT, [_P, _INT]),

@@ -13,6 +13,7 @@
 
 #include "context.h"
 #include "field29.h"
+#include "sort.h"
 
 namespace {
 
@@ -98,6 +99,54 @@ __global__ void __launch_bounds__(256) k_prod_asm_check(uint32_t n, uint32_t see
     if (e2) atomicAdd(mism + 2, 1u);
 }
 
+// The in-place forms (mul29_asm_ip: a = a b; mul29_sum2_asm_ip: c = a b + c d; tied read-write
+// operands, the hot loop's register arrangement) against the same column-block products, on the
+// operands k_prod_asm_check draws (same generator and order) at the out-of-place contracts' limb
+// bounds -- prod_asm.h states no narrower contract for the in-place forms.  The operand a
+// statement overwrites is copied first.  mism[k]: 0 mul, 1 sum2.
+__global__ void __launch_bounds__(256) k_prod_asm_ip_check(uint32_t n, uint32_t seed, uint32_t* mism) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    uint32_t s = (t ^ seed) * 2654435761u + 0x9e3779b9u;
+    auto rnd = [&](uint32_t bits) {
+        s ^= s << 13;
+        s ^= s >> 17;
+        s ^= s << 5;
+        const uint32_t m = (1u << bits) - 1;
+        return (t & 1) ? m : (s * 2654435761u) & m;
+    };
+    F29 a, b, c, d;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        a.l[i] = rnd(30);
+        b.l[i] = rnd(30);
+    }
+    const F29 m1 = mul29<FqP>(a, b);
+    F29 m2 = a;
+    mul29_asm_ip<FqP>(m2, b);
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        a.l[i] = rnd(29);
+        b.l[i] = rnd(31);
+        c.l[i] = rnd(29);
+        d.l[i] = rnd(29);
+    }
+    const F29 s1 = mul29_sum2<FqP>(a, b, c, d);
+    F29 s2 = c;
+    mul29_sum2_asm_ip<FqP>(a, b, s2, d);
+    uint32_t e0 = 0, e1 = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        e0 |= m1.l[i] ^ m2.l[i];
+        e1 |= s1.l[i] ^ s2.l[i];
+    }
+    if (e0) atomicAdd(mism + 0, 1u);
+    if (e1) atomicAdd(mism + 1, 1u);
+}
+
+// largest input of the stage diagnostics (2^24 pairs: 64 MiB per array)
+constexpr uint64_t DIAG_MAX_N = 1ull << 24;
+
 int finish(eon_ctx* ctx, const Status& s) {
     if (s.bad()) ctx->last_error = s.msg;
     return s.code;
@@ -173,6 +222,102 @@ extern "C" int eon_diag_prod_asm_check(eon_ctx* ctx, uint32_t n, uint32_t seed, 
                                   cnt.as<uint32_t>());
         EON_HIP(hipGetLastError());
         EON_HIP(hipMemcpyAsync(mismatches, cnt.p, 12, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+extern "C" int eon_diag_prod_asm_ip_check(eon_ctx* ctx, uint32_t n, uint32_t seed, uint32_t mismatches[2]) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (!mismatches) return Status::err(EON_E_ARG, "null argument");
+        DevBuf cnt;
+        PoolScope ps(ctx->pool, ctx->stream);
+        EON_HIP(ps.take(cnt, 64));
+        EON_HIP(hipMemsetAsync(cnt.p, 0, 16, ctx->stream));
+        if (n) hipLaunchKernelGGL(k_prod_asm_ip_check, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, seed,
+                                  cnt.as<uint32_t>());
+        EON_HIP(hipGetLastError());
+        EON_HIP(hipMemcpyAsync(mismatches, cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+extern "C" int eon_diag_radix_sort_pairs(eon_ctx* ctx, const uint32_t* keys, const uint32_t* vals, uint64_t n,
+                                         uint32_t bits, uint32_t* keys_out, uint32_t* vals_out) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (n > DIAG_MAX_N) return Status::err(EON_E_ARG, "at most 2^24 pairs");
+        if (bits > 32) return Status::err(EON_E_ARG, "at most 32 key bits");
+        if (n && (!keys || !vals || !keys_out || !vals_out)) return Status::err(EON_E_ARG, "null argument");
+        if (n == 0) return Status::ok();
+        DevBuf k, v, k2, v2, temp;
+        PoolScope ps(ctx->pool, ctx->stream);
+        for (DevBuf* b : {&k, &v, &k2, &v2}) EON_HIP(ps.take(*b, n * 4));
+        EON_HIP(ps.take(temp, radix_sort_temp_bytes(n, bits)));
+        EON_HIP(hipMemcpyAsync(k.p, keys, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        EON_HIP(hipMemcpyAsync(v.p, vals, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        EON_HIP(radix_sort_pairs(temp.p, k.as<uint32_t>(), k2.as<uint32_t>(), v.as<uint32_t>(), v2.as<uint32_t>(), n,
+                                 bits, ctx->stream));
+        EON_HIP(hipMemcpyAsync(keys_out, k2.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipMemcpyAsync(vals_out, v2.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+extern "C" int eon_diag_exclusive_scan_u32(eon_ctx* ctx, const uint32_t* in, uint64_t n, uint32_t* out) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (n > DIAG_MAX_N) return Status::err(EON_E_ARG, "at most 2^24 elements");
+        if (n && (!in || !out)) return Status::err(EON_E_ARG, "null argument");
+        if (n == 0) return Status::ok();
+        DevBuf a, b, temp;
+        PoolScope ps(ctx->pool, ctx->stream);
+        EON_HIP(ps.take(a, n * 4));
+        EON_HIP(ps.take(b, n * 4));
+        EON_HIP(ps.take(temp, exclusive_scan_temp_bytes(n)));
+        EON_HIP(hipMemcpyAsync(a.p, in, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        EON_HIP(exclusive_scan_u32(temp.p, a.as<uint32_t>(), b.as<uint32_t>(), n, ctx->stream));
+        EON_HIP(hipMemcpyAsync(out, b.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+extern "C" int eon_diag_scan_chunk_counts(eon_ctx* ctx, const uint32_t* start, uint32_t nb, uint32_t log_chunk,
+                                          uint32_t* out, uint32_t* max_out) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (nb > DIAG_MAX_N) return Status::err(EON_E_ARG, "at most 2^24 buckets");
+        if (log_chunk > 31) return Status::err(EON_E_ARG, "log_chunk < 32");
+        if (!start || !out || !max_out) return Status::err(EON_E_ARG, "null argument");
+        const uint64_t m = (uint64_t)nb + 1;
+        DevBuf a, b, temp, mx;
+        PoolScope ps(ctx->pool, ctx->stream);
+        EON_HIP(ps.take(a, m * 4));
+        EON_HIP(ps.take(b, m * 4));
+        EON_HIP(ps.take(temp, exclusive_scan_temp_bytes(m)));
+        EON_HIP(ps.take(mx, 64));
+        EON_HIP(hipMemcpyAsync(a.p, start, m * 4, hipMemcpyHostToDevice, ctx->stream));
+        EON_HIP(hipMemsetAsync(mx.p, 0, 16, ctx->stream));  // as batch_sort zeroes its slot (msm.hip)
+        EON_HIP(exclusive_scan_chunk_counts(temp.p, a.as<uint32_t>(), nb, log_chunk, b.as<uint32_t>(),
+                                            mx.as<uint32_t>(), ctx->stream));
+        EON_HIP(hipMemcpyAsync(out, b.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipMemcpyAsync(max_out, mx.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
     }();

@@ -1421,7 +1421,8 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
                                 out.vals2.as<uint32_t>(), E, bt.key_bits, st));
         prof->end(st);
     } else {
-        prof->begin("k_msm_digits", n * bt.cols * 32 + E * 8, st);
+        // the profile record names the kernel that runs (the stage tests assert their route by it)
+        prof->begin(quad ? "k_msm_digits4" : "k_msm_digits", n * bt.cols * 32 + E * 8, st);
         hipLaunchKernelGGL(quad ? k_msm_digits4<true> : k_msm_digits, dim3(grid_x, grid_y),
                            dim3(256), 0, st, bt.scalars, n, ld, bt.cols, bt.c, bt.W, L.W, (uint32_t)L.precomputed,
                            tile_cols, wk.keys.as<uint32_t>(), wk.vals.as<uint32_t>(), radix_sort_passes(bt.key_bits),
@@ -1764,6 +1765,10 @@ struct eon_msm_scalars {
     eon::MsmLayout layout;
     std::vector<eon::Batch> batches;
     std::vector<eon::SortedBufs> sorted;
+    // diagnostics only (eon_diag_msm_g1_prepare_active_dev): digitise a single column's active
+    // windows as the unprepared single MSM does, so that its batch can be read back; false for every
+    // handle the product path makes
+    bool active_windows = false;
     // buffers go back to the context's cache (caller holds ctx->mu)
     ~eon_msm_scalars() {
         constexpr size_t CAP = 48ull << 30;  // MSM_SORTED_CACHE_CAP
@@ -1986,7 +1991,7 @@ Status msm_run_columns(eon_ctx* ctx, const eon_msm_bases* b, const Fr* scalars, 
     // carries at most one bit past it): scalars < 2^64, as in kzg/benches, need 5 of 16 windows
     // of 16 bits.  One OR-reduction over the scalars and a 32-byte read-back.
     static const bool all_windows = getenv("EON_MSM_ALL_WINDOWS") != nullptr;
-    if (width == 1 && !keep && !all_windows) {
+    if (width == 1 && (!keep || keep->active_windows) && !all_windows) {
         constexpr size_t or_bytes = SCALAR_OR_COPIES * 8 * 4;
         EON_HIP(ctx->msm.stat.ensure(std::max<size_t>(64, or_bytes)));
         EON_HIP(hipMemsetAsync(ctx->msm.stat.p, 0, or_bytes, ctx->stream));
@@ -2279,6 +2284,76 @@ int eon_msm_g1_columns_prepared(eon_ctx* ctx, const eon_msm_bases* const* bases,
     if (!s.bad())
         for (uint64_t j = 0; j < total; j++) out[j] = g1_to_abi(r[j]);
     return finish(ctx, s);
+}
+
+// Diagnostics (tests): what a prepared handle keeps of its batches, read back.  Reads only.
+int eon_diag_msm_scalars_batches(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t* count) {
+    if (!ctx) return EON_E_ARG;
+    if (!prepared || !count) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (prepared->ctx && prepared->ctx != ctx) return finish(ctx, Status::err(EON_E_ARG, "prepared scalars of another context"));
+    *count = (uint32_t)prepared->batches.size();
+    return EON_OK;
+}
+
+int eon_diag_msm_scalars_batch(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t k, eon_msm_batch_info* info,
+                               uint32_t* keys, uint32_t* vals, uint32_t* start, uint32_t* piece_off) {
+    if (!ctx) return EON_E_ARG;
+    if (!prepared || !info) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (prepared->ctx && prepared->ctx != ctx) return Status::err(EON_E_ARG, "prepared scalars of another context");
+        if (k >= prepared->batches.size() || k >= prepared->sorted.size())
+            return Status::err(EON_E_ARG, "batch index out of range");
+        const Batch& bt = prepared->batches[k];
+        if (!bt.counted) return Status::err(EON_E_ARG, "the batch's counts were never read back");
+        info->pairs = bt.E;
+        info->c = bt.c;
+        info->windows = bt.W;
+        info->ref_windows = prepared->layout.W;
+        info->groups = bt.groups;
+        info->nb = bt.nb;
+        info->log_chunk = bt.log_chunk;
+        info->cols = bt.cols;
+        info->col0 = bt.col0;
+        info->n_pairs = bt.n_pairs;
+        info->n_pieces = bt.n_pieces;
+        const SortedBufs& sb = prepared->sorted[k];
+        const size_t pair_bytes = bt.E * 4, bucket_bytes = ((size_t)bt.nb + 1) * 4;
+        if (sb.keys2.bytes < pair_bytes || sb.vals2.bytes < pair_bytes || sb.start.bytes < bucket_bytes ||
+            sb.piece_off.bytes < bucket_bytes)
+            return Status::err(EON_E_ARG, "the batch's sorted buffers are not held");
+        // the prepare call returned after its streams had drained into the context stream
+        if (keys) EON_HIP(hipMemcpyAsync(keys, sb.keys2.p, pair_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (vals) EON_HIP(hipMemcpyAsync(vals, sb.vals2.p, pair_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (start) EON_HIP(hipMemcpyAsync(start, sb.start.p, bucket_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (piece_off)
+            EON_HIP(hipMemcpyAsync(piece_off, sb.piece_off.p, bucket_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+// The unprepared single MSM (msm_run with its active-window truncation) that also keeps its batch.
+int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases, const eon_fr* scalars, uint64_t n,
+                                       eon_g1_affine* out, eon_msm_scalars** prepared) {
+    if (!ctx) return EON_E_ARG;
+    if (!bases || !out || !prepared || (n && !scalars)) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    auto* keep = new eon_msm_scalars();
+    keep->active_windows = true;
+    G1Affine r;
+    Status s = msm_run_columns(ctx, bases, reinterpret_cast<const Fr*>(scalars), n, 1, &r, keep);
+    if (s.bad()) {
+        delete keep;
+        return finish(ctx, s);
+    }
+    *out = g1_to_abi(r);
+    *prepared = keep;
+    return EON_OK;
 }
 
 int eon_g1_multi_exp(eon_ctx* ctx, const eon_g1_affine* points, const eon_fr* scalars, uint64_t n,

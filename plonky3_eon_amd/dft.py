@@ -87,6 +87,44 @@ class Context:
         self.check(self.lib.eon_diag_prod_asm_check(self._h, int(n), int(seed), r))
         return list(r)
 
+    def prod_asm_ip_check(self, n: int = 1 << 20, seed: int = 1) -> list:
+        """Diagnostic (eon_diag_prod_asm_ip_check): mismatching cases of the in-place whole-product
+        asm statements (mul, sum2) against the column-block products, n operands each."""
+        r = (ctypes.c_uint32 * 2)()
+        self.check(self.lib.eon_diag_prod_asm_ip_check(self._h, int(n), int(seed), r))
+        return list(r)
+
+    def diag_radix_sort_pairs(self, keys, vals, bits: int):
+        """Diagnostic (eon_diag_radix_sort_pairs): the MSM's stable radix sort of (u32 key, u32 value)
+        host pairs on the low `bits` key bits -> (keys_out, vals_out)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        v = np.ascontiguousarray(vals, dtype=np.uint32)
+        if k.shape != v.shape or k.ndim != 1:
+            raise ValueError("keys and vals must be 1-d arrays of one length")
+        ko, vo = np.zeros_like(k), np.zeros_like(v)
+        p = [a.ctypes.data_as(ctypes.c_void_p) for a in (k, v, ko, vo)]
+        self.check(self.lib.eon_diag_radix_sort_pairs(self._h, p[0], p[1], k.shape[0], int(bits), p[2], p[3]))
+        return ko, vo
+
+    def diag_exclusive_scan_u32(self, values) -> np.ndarray:
+        """Diagnostic (eon_diag_exclusive_scan_u32): out[i] = values[0] + ... + values[i-1] mod 2^32."""
+        v = np.ascontiguousarray(values, dtype=np.uint32)
+        out = np.zeros_like(v)
+        self.check(self.lib.eon_diag_exclusive_scan_u32(self._h, v.ctypes.data_as(ctypes.c_void_p), v.shape[0],
+                                                        out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def diag_scan_chunk_counts(self, start, log_chunk: int):
+        """Diagnostic (eon_diag_scan_chunk_counts): the MSM's piece offsets of the nb + 1 bucket starts
+        -> (nb + 1 offsets, the largest count if above 1 else 0)."""
+        s = np.ascontiguousarray(start, dtype=np.uint32)
+        out = np.zeros_like(s)
+        mx = ctypes.c_uint32()
+        self.check(self.lib.eon_diag_scan_chunk_counts(self._h, s.ctypes.data_as(ctypes.c_void_p), s.shape[0] - 1,
+                                                       int(log_chunk), out.ctypes.data_as(ctypes.c_void_p),
+                                                       ctypes.byref(mx)))
+        return out, mx.value
+
     def close(self):
         if getattr(self, "_h", None):
             self.lib.eon_ctx_destroy(self._h)

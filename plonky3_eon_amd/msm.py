@@ -94,6 +94,21 @@ class MsmBases:
                                                      ctypes.byref(h)))
         return (out if want_commitments else None), PreparedScalars(h, rows, width, ctx)
 
+    def diag_msm_keep_batch(self, scalars):
+        """Diagnostic (eon_diag_msm_g1_prepare_active_dev): the single MSM of a device (n, 4) Fr column
+        as ``msm`` runs it -- only the windows its largest scalar reaches are digitised -- that also
+        keeps its batch for ``PreparedScalars.read_batch`` -> (point (8,), prep)."""
+        import torch
+
+        lib, ctx = self.ctx.lib, self.ctx
+        s = scalars.contiguous()
+        out = np.zeros(8, dtype=np.uint64)
+        ctx.set_stream(torch.cuda.current_stream(s.device).cuda_stream)
+        h = ctypes.c_void_p()
+        ctx.check(lib.eon_diag_msm_g1_prepare_active_dev(ctx.handle, self._h, ctypes.c_void_p(s.data_ptr()),
+                                                         int(s.shape[0]), _p(out), ctypes.byref(h)))
+        return out, PreparedScalars(h, int(s.shape[0]), 1, ctx)
+
     def opening_bases(self, n: int, point) -> "MsmBases":
         """KZG opening bases for `point` (Fr limbs or int, Montgomery via fr_to_abi) over the
         first n - 1 bases (eon_kzg_opening_bases_create)."""
@@ -140,6 +155,28 @@ class PreparedScalars:
         self.ctx.check(self.ctx.lib.eon_msm_g1_columns_prepared(self.ctx.handle, arr, len(bases_list), self._h,
                                                                 _p(out)))
         return out
+
+    def num_batches(self) -> int:
+        """Diagnostic (eon_diag_msm_scalars_batches): the column batches the matrix was sorted in."""
+        k = ctypes.c_uint32()
+        self.ctx.check(self.ctx.lib.eon_diag_msm_scalars_batches(self.ctx.handle, self._h, ctypes.byref(k)))
+        return k.value
+
+    def read_batch(self, k: int, arrays: bool = True) -> dict:
+        """Diagnostic (eon_diag_msm_scalars_batch): batch k's layout (eon_msm_batch_info's fields) and,
+        with `arrays`, its kept device arrays: the sorted `keys` / `vals` (`pairs` entries each) and
+        the bucket `start` / `piece_off` (nb + 1 entries each)."""
+        lib, ctx = self.ctx.lib, self.ctx
+        info = _lib.eon_msm_batch_info()
+        ctx.check(lib.eon_diag_msm_scalars_batch(ctx.handle, self._h, int(k), ctypes.byref(info), None, None, None,
+                                                 None))
+        r = {f: int(getattr(info, f)) for f, _ in info._fields_}
+        if arrays:
+            r["keys"], r["vals"] = np.zeros(r["pairs"], np.uint32), np.zeros(r["pairs"], np.uint32)
+            r["start"], r["piece_off"] = np.zeros(r["nb"] + 1, np.uint32), np.zeros(r["nb"] + 1, np.uint32)
+            ctx.check(lib.eon_diag_msm_scalars_batch(ctx.handle, self._h, int(k), ctypes.byref(info), _p(r["keys"]),
+                                                     _p(r["vals"]), _p(r["start"]), _p(r["piece_off"])))
+        return r
 
     def close(self):
         if getattr(self, "_h", None):

@@ -52,3 +52,12 @@ def test_prod_asm_matches_column_products(gpu_ctx):
     contracts' limb bounds, half of them with every limb at its maximum."""
     for seed in (1, 2, 3, 4):
         assert gpu_ctx.prod_asm_check(1 << 20, seed) == [0, 0, 0]
+
+
+def test_prod_asm_in_place_matches_column_products(gpu_ctx):
+    """The in-place forms the piece sums' hot loop runs (mul29_asm_ip, mul29_sum2_asm_ip: tied
+    read-write operands, another register arrangement than the out-of-place statements above) equal
+    the column-block mul29 / mul29_sum2 bit for bit on 2^22 operands of each kind at the same limb
+    bounds, half of them with every limb at its maximum."""
+    for seed in (1, 2, 3, 4):
+        assert gpu_ctx.prod_asm_ip_check(1 << 20, seed) == [0, 0]

@@ -173,6 +173,11 @@ def test_native_prove_fiat_shamir_vs_oracle(gpu_ctx, consts, log_n, vl):
     pp = prove(air, GpuKzgPcs(n, 12345, gpu_ctx), trace, None, None, challenger=ch2)
     assert (pp.alpha, pp.zeta) == (want["alpha"], want["zeta"])
     np.testing.assert_array_equal(pp.opened[0].witnesses[0][1], want["trace_open"][1][1])
+    assert_proof_equals_oracle(proof, want)
+
+
+def assert_proof_equals_oracle(proof, want):
+    """Every commitment, opened value and witness of a native proof against the oracle's."""
     np.testing.assert_array_equal(proof.trace_commit[0], want["trace_commit"])
     np.testing.assert_array_equal(np.stack([c[0] for c in proof.quotient_commit]), want["quotient_commit"])
     tr = proof.opened[0]
@@ -183,6 +188,50 @@ def test_native_prove_fiat_shamir_vs_oracle(gpu_ctx, consts, log_n, vl):
     for c in range(2):
         np.testing.assert_array_equal(qo.values[c][0], want["quotient_open"][c][0][0])
         np.testing.assert_array_equal(qo.witnesses[c][0], want["quotient_open"][c][1][0])
+
+
+@pytest.mark.parametrize("log_n,vl", [(10, 1), (10, 2)])
+def test_native_prove_fiat_shamir_vs_oracle_fused_routes(gpu_ctx, consts, monkeypatch, log_n, vl):
+    """The same byte-for-byte parity at 2^10 rows with the window width forced to the headline
+    prove's c = 16 (EON_MSM_FORCE_C): the commit and open MSMs then run the fused digit sort
+    (k_digit_sort_pass, whole 1024-row tiles) and, with 64 groups (columns) or more in a batch, the
+    call-wide fused bucket reduction -- routes the 2^3..2^5-row parity tests above never reach.  VECTOR_LEN 2, not
+    8: the oracle's 2^10-row prove at VECTOR_LEN 8 measured 12.6 s on the GPU host (1.6 s at
+    VECTOR_LEN 1), above the 10 s this test allows itself."""
+    import time
+
+    import torch
+
+    from plonky3_eon_amd.air import Poseidon2Air
+    from plonky3_eon_amd.native import Challenger, NativeKzgPcs, Poseidon2Constants, prove_native
+
+    monkeypatch.setenv("EON_MSM_FORCE_C", "16")
+    n = 1 << log_n
+    pcs = NativeKzgPcs(n, 12345, gpu_ctx)
+    air = Poseidon2Air(consts.begin, consts.partial, consts.end, vl, gpu_ctx)
+    inputs = C.random_fr(log_n * 5 + vl, n * vl * 3).reshape(n * vl, 3, 4)
+    trace = air.generate_trace(torch.from_numpy(inputs.view(np.int64)).to("cuda:0"))
+    pyc = O.p2_constants(99, 2, 22)
+    ch = Challenger(Poseidon2Constants([[lim(x) for x in r] for r in pyc[0]], [lim(x) for x in pyc[1]],
+                                       [[lim(x) for x in r] for r in pyc[2]]))
+    gpu_ctx.profile(True)
+    try:
+        proof = prove_native(air, pcs, trace, None, None, challenger=ch)
+        kernels = gpu_ctx.profile_report()
+    finally:
+        gpu_ctx.profile(False)
+    assert "k_digit_sort_pass" in kernels, sorted(kernels)
+    assert "k_group_finish" in kernels, sorted(kernels)  # >= 64 groups: the call-wide fused reduction
+
+    ref = O.DuplexChallenger(pyc)
+    srs = C.g1_srs(n + 1, C.fr_from_u64(12345))
+    t0 = time.perf_counter()
+    want = prove_oracle.prove(C.p2_generate_trace(inputs, vl, consts), srs, consts, vl, None, None,
+                              challenger=ref)
+    print(f"oracle prove log_n={log_n} vl={vl}: {time.perf_counter() - t0:.2f} s")
+    assert (proof.alpha, proof.zeta) == (want["alpha"], want["zeta"])
+    np.testing.assert_array_equal(ch.state(), np.stack([lim(x) for x in ref.state]))
+    assert_proof_equals_oracle(proof, want)
 
 
 def test_native_errors(gpu_ctx, consts):
