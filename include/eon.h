@@ -173,6 +173,38 @@ int eon_diag_radix_sort_pairs(eon_ctx* ctx, const uint32_t* keys, const uint32_t
 int eon_diag_exclusive_scan_u32(eon_ctx* ctx, const uint32_t* in, uint64_t n, uint32_t* out);
 int eon_diag_scan_chunk_counts(eon_ctx* ctx, const uint32_t* start, uint32_t nb, uint32_t log_chunk, uint32_t* out,
                                uint32_t* max_out);
+/* One radix-2^29 curve formula of the MSM bucket sums (csrc/ec29.h) per thread, on n independent
+ * cases (tests; host pointers, synchronous, scratch from the context's pool; n <= 2^20).
+ * `acc` and `acc_out` are n raw accumulators of 36 words: X, Y, ZZ, ZZZ as 9 limbs of 29 bits each
+ * (value sum l[i] 2^(29 i), x 2^261 mod q), raw ZZ == 0 meaning the identity; they are read and
+ * written with the bucket sums' own load and store.  `arg` is per case an affine base as 18 words
+ * (x then y, 9 limbs each, passed to the formula as they are) or a second raw accumulator of 36
+ * words, by `op`:
+ *    0 madd29            acc += arg(18); code = its return (0: exceptional, acc unchanged)
+ *    1 madd29_unchecked  acc += arg(18); code 0
+ *    2 madd29_negsum     acc = the tuple of -(acc + arg(18)); code 0
+ *    3 madd29_exceptional(acc, arg(18)); code = its return (1: the sum is the identity)
+ *    4 dbl29_affine      acc_out = 2 arg(18); `acc` is not read and may be NULL
+ *    5 dbl29             acc = 2 acc; no arg
+ *    6 add29             acc += arg(36); code = its return 0 / 1 / 2
+ *    7 add29_ilp         the same
+ *    8 dbl29_ilp         acc = 2 acc; no arg
+ *    9 acc29             acc += arg(36) with the identity flags of both raw inputs; code = the
+ *                        resulting flag, an identity is stored as 36 zero words
+ *   10 acc29_ilp         the same
+ *   11 raw29_to_xyzz     words 0..31 of acc_out = the canonical radix-2^32 Montgomery X, Y, ZZ, ZZZ
+ *                        (8 words each), words 32..35 zero; code = 1 for the identity; no arg
+ *   12 to_fq261(to_fq256(c)) of each of acc's four coordinates c, as 256-bit integers in words
+ *                        0..31 of acc_out, words 32..35 zero; code 0; no arg
+ *   13 neg29_lazy        X = 2q - X and ZZZ = 3q - ZZZ limb by limb (X < q, ZZZ < 2q, normalised),
+ *                        the piece loop's negations of a base's y and of a flushed ZZZ; Y and ZZ
+ *                        pass through; code 0; no arg
+ *   14 x29_to_xyzz       as 11, from the loaded accumulator and its identity flag
+ * An `arg` that `op` does not read may be NULL.  EON_E_ARG for an unknown op, n > 2^20, or a NULL
+ * pointer that is read or written with n > 0.  The formulas' preconditions (non-identity inputs,
+ * coordinate bounds) are the caller's. */
+int eon_diag_ec29_op(eon_ctx* ctx, uint32_t op, const uint32_t* acc, const uint32_t* arg, uint64_t n,
+                     uint32_t* acc_out, int32_t* code_out);
 /* What a prepared handle (eon_msm_g1_columns_prepare_dev) keeps of its column batches.  A batch
  * covers columns [col0, col0 + cols) with window width c and `windows` digit windows per scalar;
  * `ref_windows` is the window count of the bases' layout (a fixed-base reference is row *
@@ -212,6 +244,7 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   8: eon_diag_ec29_op, the curve formulas of the MSM bucket sums one per thread, additive;
  *   7: the eon_diag_* stage diagnostics of the MSM digit pipeline and eon_msm_batch_info, additive;
  *   6: the LogUp lookup entry points eon_air_program_create_lk / eon_quotient_values_lk_dev /
  *      eon_lookup_permutation_dev, additive;

@@ -23,7 +23,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 7  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 8  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -106,6 +106,7 @@ SIGNATURES = {
     "eon_diag_radix_sort_pairs": (_INT, [_P, _P, _P, _U64, _U32, _P, _P]),
     "eon_diag_exclusive_scan_u32": (_INT, [_P, _P, _U64, _P]),
     "eon_diag_scan_chunk_counts": (_INT, [_P, _P, _U32, _U32, _P, _P]),
+    "eon_diag_ec29_op": (_INT, [_P, _U32, _P, _P, _U64, _P, _P]),
     "eon_diag_msm_g1_prepare_active_dev": (_INT, [_P, _P, _P, _U64, _P, ctypes.POINTER(_P)]),
     "eon_diag_msm_scalars_batches": (_INT, [_P, _P, _P]),
     "eon_diag_msm_scalars_batch": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _P]),

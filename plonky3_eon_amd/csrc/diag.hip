@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "context.h"
+#include "ec29.h"
 #include "field29.h"
 #include "sort.h"
 
@@ -144,8 +145,136 @@ __global__ void __launch_bounds__(256) k_prod_asm_ip_check(uint32_t n, uint32_t 
     if (e1) atomicAdd(mism + 1, 1u);
 }
 
+// One ec29.h formula per thread (eon_diag_ec29_op): thread t reads accumulator acc[t] (ld_raw29)
+// and its argument -- an affine base as 18 limbs (x, y; read as they are, so y may be a lazy
+// negation) or a second raw accumulator -- runs the formula once and stores the accumulator
+// (st_raw29) and the formula's return value.  One kernel per formula, 64-thread blocks: each gets
+// the register allocation it would get on its own, tied-operand asm products included.
+enum : uint32_t {
+    EC29_MADD = 0,
+    EC29_MADD_UNCHECKED,
+    EC29_MADD_NEGSUM,
+    EC29_MADD_EXCEPTIONAL,
+    EC29_DBL_AFFINE,
+    EC29_DBL,
+    EC29_ADD,
+    EC29_ADD_ILP,
+    EC29_DBL_ILP,
+    EC29_ACC,
+    EC29_ACC_ILP,
+    EC29_TO_XYZZ,
+    EC29_ROUNDTRIP,
+    EC29_NEG_LAZY,
+    EC29_X29_TO_XYZZ,
+    EC29_OPS
+};
+// words of one argument: 18 (affine x, y), 36 (raw accumulator) or 0 (none)
+constexpr uint32_t ec29_arg_words(uint32_t op) {
+    return op <= EC29_DBL_AFFINE ? 18u
+           : op == EC29_ADD || op == EC29_ADD_ILP || op == EC29_ACC || op == EC29_ACC_ILP ? 36u
+                                                                                          : 0u;
+}
+
+__device__ __forceinline__ F29 ld_limbs29(const uint32_t* p) {
+    F29 r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = p[i];
+    pin29(r);
+    return r;
+}
+
+__device__ __forceinline__ void st_words8(uint32_t* p, const Fq& a) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) p[i] = a.v[i];
+}
+
+template <uint32_t OP>
+__global__ void __launch_bounds__(64) k_ec29_op(const G1Raw29* acc, const uint32_t* arg, uint32_t n, G1Raw29* out,
+                                                int32_t* code) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    if constexpr (OP == EC29_TO_XYZZ || OP == EC29_X29_TO_XYZZ) {
+        // the four canonical radix-2^32 coordinates in words 0..31, code = identity: of the raw
+        // accumulator (raw29_to_xyzz), or of the loaded one and its flag (x29_to_xyzz)
+        G1Xyzz r;
+        if constexpr (OP == EC29_TO_XYZZ) {
+            r = raw29_to_xyzz(acc + t);
+        } else {
+            G1X29 a;
+            const bool a_inf = ld_raw29(acc + t, a);
+            r = x29_to_xyzz(a, a_inf);
+        }
+        uint32_t* w = out[t].w;
+        st_words8(w, r.X);
+        st_words8(w + 8, r.Y);
+        st_words8(w + 16, r.ZZ);
+        st_words8(w + 24, r.ZZZ);
+#pragma unroll
+        for (int i = 32; i < 36; i++) w[i] = 0;
+        code[t] = is_inf(r) ? 1 : 0;
+    } else if constexpr (OP == EC29_ROUNDTRIP) {
+        // to_fq261(to_fq256(c)) of each coordinate c as a 256-bit integer, words 0..31
+        G1X29 a;
+        ld_raw29(acc + t, a);
+        uint32_t* w = out[t].w;
+        st_words8(w, to_fq261(to_fq256(a.X)));
+        st_words8(w + 8, to_fq261(to_fq256(a.Y)));
+        st_words8(w + 16, to_fq261(to_fq256(a.ZZ)));
+        st_words8(w + 24, to_fq261(to_fq256(a.ZZZ)));
+#pragma unroll
+        for (int i = 32; i < 36; i++) w[i] = 0;
+        code[t] = 0;
+    } else {
+        G1X29 a;
+        bool a_inf = false;
+        int rc = 0;
+        if constexpr (OP != EC29_DBL_AFFINE) a_inf = ld_raw29(acc + t, a);
+        if constexpr (ec29_arg_words(OP) == 18) {
+            const F29 x = ld_limbs29(arg + (uint64_t)t * 18), y = ld_limbs29(arg + (uint64_t)t * 18 + 9);
+            if constexpr (OP == EC29_MADD) rc = madd29(a, x, y);
+            if constexpr (OP == EC29_MADD_UNCHECKED) madd29_unchecked(a, x, y);
+            if constexpr (OP == EC29_MADD_NEGSUM) madd29_negsum(a, x, y);
+            if constexpr (OP == EC29_MADD_EXCEPTIONAL) rc = madd29_exceptional(a, x, y);
+            if constexpr (OP == EC29_DBL_AFFINE) a = dbl29_affine(x, y);
+        } else if constexpr (ec29_arg_words(OP) == 36) {
+            G1X29 q;
+            const bool q_inf = ld_raw29(reinterpret_cast<const G1Raw29*>(arg) + t, q);
+            if constexpr (OP == EC29_ADD) rc = add29(a, q);
+            if constexpr (OP == EC29_ADD_ILP) rc = add29_ilp(a, q);
+            if constexpr (OP == EC29_ACC) acc29(a, a_inf, q, q_inf);
+            if constexpr (OP == EC29_ACC_ILP) acc29_ilp(a, a_inf, q, q_inf);
+            if constexpr (OP == EC29_ACC || OP == EC29_ACC_ILP) rc = a_inf;
+        } else {
+            if constexpr (OP == EC29_DBL) dbl29(a);
+            if constexpr (OP == EC29_DBL_ILP) dbl29_ilp(a);
+            if constexpr (OP == EC29_NEG_LAZY) {  // the piece loop's two lazy negations
+                a.X = neg29_lazy<2>(a.X);
+                a.ZZZ = neg29_lazy<3>(a.ZZZ);
+            }
+        }
+        if ((OP == EC29_ACC || OP == EC29_ACC_ILP) && a_inf)
+            st_raw29_inf(out + t);
+        else
+            st_raw29(out + t, a);
+        code[t] = rc;
+    }
+}
+
+template <uint32_t OP = 0>
+void launch_ec29_op(uint32_t op, const G1Raw29* acc, const uint32_t* arg, uint32_t n, G1Raw29* out, int32_t* code,
+                    hipStream_t st) {
+    if constexpr (OP < EC29_OPS) {
+        if (op == OP)
+            hipLaunchKernelGGL(k_ec29_op<OP>, dim3((n + 63) / 64), dim3(64), 0, st, acc, arg, n, out, code);
+        else
+            launch_ec29_op<OP + 1>(op, acc, arg, n, out, code, st);
+    }
+}
+
 // largest input of the stage diagnostics (2^24 pairs: 64 MiB per array)
 constexpr uint64_t DIAG_MAX_N = 1ull << 24;
+// and of the formula diagnostic (2^20 accumulators: 144 MiB per array)
+constexpr uint64_t DIAG_EC29_MAX_N = 1ull << 20;
 
 int finish(eon_ctx* ctx, const Status& s) {
     if (s.bad()) ctx->last_error = s.msg;
@@ -318,6 +447,38 @@ extern "C" int eon_diag_scan_chunk_counts(eon_ctx* ctx, const uint32_t* start, u
                                             mx.as<uint32_t>(), ctx->stream));
         EON_HIP(hipMemcpyAsync(out, b.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipMemcpyAsync(max_out, mx.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+extern "C" int eon_diag_ec29_op(eon_ctx* ctx, uint32_t op, const uint32_t* acc, const uint32_t* arg, uint64_t n,
+                                uint32_t* acc_out, int32_t* code_out) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (op >= EC29_OPS) return Status::err(EON_E_ARG, "unknown ec29 op");
+        if (n > DIAG_EC29_MAX_N) return Status::err(EON_E_ARG, "at most 2^20 accumulators");
+        const uint32_t aw = ec29_arg_words(op);
+        const bool uses_acc = op != EC29_DBL_AFFINE;
+        if (n && ((uses_acc && !acc) || (aw && !arg) || !acc_out || !code_out))
+            return Status::err(EON_E_ARG, "null argument");
+        if (n == 0) return Status::ok();
+        DevBuf a, b, o, c;
+        PoolScope ps(ctx->pool, ctx->stream);
+        EON_HIP(ps.take(a, n * sizeof(G1Raw29)));
+        EON_HIP(ps.take(b, n * sizeof(G1Raw29)));
+        EON_HIP(ps.take(o, n * sizeof(G1Raw29)));
+        EON_HIP(ps.take(c, n * sizeof(int32_t)));
+        if (uses_acc) EON_HIP(hipMemcpyAsync(a.p, acc, n * sizeof(G1Raw29), hipMemcpyHostToDevice, ctx->stream));
+        if (aw) EON_HIP(hipMemcpyAsync(b.p, arg, n * aw * 4, hipMemcpyHostToDevice, ctx->stream));
+        launch_ec29_op(op, a.as<G1Raw29>(), b.as<uint32_t>(), (uint32_t)n, o.as<G1Raw29>(), c.as<int32_t>(),
+                       ctx->stream);
+        EON_HIP(hipGetLastError());
+        EON_HIP(hipMemcpyAsync(acc_out, o.p, n * sizeof(G1Raw29), hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipMemcpyAsync(code_out, c.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
     }();

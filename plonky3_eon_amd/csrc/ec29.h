@@ -48,6 +48,11 @@ __device__ __forceinline__ G1X29 dbl29_affine(const F29& x, const F29& y) {
 // becomes 0 mod p and stays 0 under every later unchecked addition (ZZ' = ZZ PP), while a genuine
 // sum never has ZZ = 0 (a product of nonzero PPs).  A caller summing a run of bases tests ZZ once
 // at the end of the run and re-sums it with the checked form when it is 0.
+//
+// Inputs: acc.X < 8p, acc.Y < 4p, acc.ZZ < 2p, acc.ZZZ < 2p, all normalised -- narrower than the
+// invariant for ZZZ: every caller (piece_run29, k_piece_sum29, k_triple29) builds acc in registers
+// from a base, an earlier madd29* or dbl29_affine, so the lazily negated ZZZ of a stored piece
+// never arrives here (nor at madd29_negsum / madd29_exceptional).  ax, ay canonical.
 template <bool CHECK = true>
 __device__ __forceinline__ bool madd29(G1X29& acc, const F29& ax, const F29& ay) {
     const F29 U2 = mul29<FqP>(ax, acc.ZZ);            // < 2p
@@ -175,6 +180,9 @@ __device__ __forceinline__ int add29(G1X29& p, const G1X29& q) {
 // add29 / dbl29 with their independent products issued together (mul29_n): 5 / 4 dependent
 // product steps instead of 14 / 10, for latency-bound callers (a wave alone on its SIMD).  Same
 // group element, same bounds on the result (X < 8p, Y < 4p, ZZ, ZZZ < 2p), same return codes.
+// Like add29 / dbl29 they take the whole invariant, a lazily negated ZZZ on either side included
+// (k_bucket_sums29 hands a one-piece bucket's raw piece on to k_segment_sum29 as it is): ZZZ only
+// ever enters mul29_n, whose operands may have limbs < 2^30.
 __device__ __forceinline__ int add29_ilp(G1X29& p, const G1X29& q) {
     F29 t[4];
     mul29_n<FqP, 4>({p.X, q.X, p.Y, q.Y}, {q.ZZ, p.ZZ, q.ZZZ, p.ZZZ}, t);

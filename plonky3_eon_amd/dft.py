@@ -94,6 +94,25 @@ class Context:
         self.check(self.lib.eon_diag_prod_asm_ip_check(self._h, int(n), int(seed), r))
         return list(r)
 
+    EC29_OPS = ("madd", "madd_unchecked", "madd_negsum", "madd_exceptional", "dbl_affine", "dbl", "add", "add_ilp",
+                "dbl_ilp", "acc", "acc_ilp", "to_xyzz", "roundtrip", "neg_lazy", "x29_to_xyzz")
+
+    def diag_ec29_op(self, op: str, acc, arg=None):
+        """Diagnostic (eon_diag_ec29_op): one radix-2^29 curve formula of the MSM bucket sums per case.
+        `acc` is (n, 36) u32 raw accumulators (None for "dbl_affine"), `arg` (n, 18) affine limbs or
+        (n, 36) raw accumulators where `op` takes one -> ((n, 36) u32 output, (n,) i32 return codes)."""
+        a = None if acc is None else np.ascontiguousarray(acc, dtype=np.uint32)
+        b = None if arg is None else np.ascontiguousarray(arg, dtype=np.uint32)
+        n = (a if a is not None else b).shape[0]
+        for m in (a, b):
+            if m is not None and (m.ndim != 2 or m.shape[0] != n or m.shape[1] not in (18, 36)):
+                raise ValueError("acc is (n, 36), arg (n, 18) or (n, 36)")
+        out = np.zeros((n, 36), dtype=np.uint32)
+        code = np.zeros(n, dtype=np.int32)
+        p = [None if m is None else m.ctypes.data_as(ctypes.c_void_p) for m in (a, b, out, code)]
+        self.check(self.lib.eon_diag_ec29_op(self._h, self.EC29_OPS.index(op), p[0], p[1], n, p[2], p[3]))
+        return out, code
+
     def diag_radix_sort_pairs(self, keys, vals, bits: int):
         """Diagnostic (eon_diag_radix_sort_pairs): the MSM's stable radix sort of (u32 key, u32 value)
         host pairs on the low `bits` key bits -> (keys_out, vals_out)."""
