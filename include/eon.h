@@ -81,7 +81,9 @@ enum {
     EON_E_DEGREE_TOO_LARGE = -2, /* KzgError::DegreeTooLarge (kzg/src/params.rs:164-173) */
     EON_E_DEVICE = -3,           /* HIP runtime error */
     EON_E_OOM = -4,              /* device allocation failed */
-    EON_E_ARG = -5               /* null pointer / invalid argument */
+    EON_E_ARG = -5,              /* null pointer / invalid argument */
+    EON_E_CONSTRAINT = -6        /* the prove driver's constraint check failed (eon_prove.h; the reference's
+                                    debug-build panic, check_constraints.rs:165-173) */
 };
 
 enum {
@@ -244,6 +246,7 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   9: eon_check_constraints_dev and eon_constraint_report, EON_E_CONSTRAINT, additive;
  *   8: eon_diag_ec29_op, the curve formulas of the MSM bucket sums one per thread, additive;
  *   7: the eon_diag_* stage diagnostics of the MSM digit pipeline and eon_msm_batch_info, additive;
  *   6: the LogUp lookup entry points eon_air_program_create_lk / eon_quotient_values_lk_dev /
@@ -559,6 +562,43 @@ int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog, const 
 int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* trace,
                                const eon_fr* pre_trace, uint64_t height, const eon_fr* publics, uint32_t n_public,
                                const eon_fr* challenges, uint32_t n_challenges, eon_fr* perm_out);
+
+/* check_constraints (eon-uni-stark/src/check_constraints.rs:22-101), what prove_with_preprocessed
+ * runs in every debug build right after the permutation trace (prover.rs:252-262), on the device:
+ * every trace row i runs the program with local = row i, next = row (i + 1) mod height (:41-47) of
+ * the main, the preprocessed (:55-69) and the permutation (:71-79) trace, all on the TRACE domain,
+ * with is_first_row / is_last_row / is_transition the field elements 1 / 0 for i == 0,
+ * i == height - 1, i != height - 1 (:88-90; not the coset selectors), and every constraint -- the
+ * AIR's, then the lookups', in assert order -- is tested for zero (assert_zero, :165-173).  The
+ * reference panics at the first failure, "Constraint failed at row R: expected zero, got V"; here
+ * every (row, constraint) is evaluated and the report carries that first failure -- the lowest row,
+ * then the lowest constraint on it -- with its value, plus the counts. */
+typedef struct {
+    uint64_t failures;             /* (row, constraint) pairs whose value is nonzero */
+    uint64_t row;                  /* first failing row; valid when failures > 0 */
+    uint32_t constraint;           /* first failing constraint on that row, assert order */
+    uint32_t failing_constraints;  /* constraints that fail on at least one row */
+    eon_fr   value;                /* that constraint's value on that row, canonical */
+} eon_constraint_report;
+/* `trace` = height x width (device, row-major), `pre_trace` = height x preprocessed_width and
+ * `perm_trace` = height x permutation_width likewise; publics / challenges host arrays;
+ * `per_constraint` (host, num_constraints entries, nullable) receives the number of rows on which
+ * each constraint fails; *out (host) the report.  EON_OK whether or not a constraint fails: the
+ * report says which (failures == 0: the trace satisfies the AIR; row, constraint and value are then
+ * zero).  The result is synchronous: the call returns after the device has finished, like the
+ * zero-denominator flag of eon_lookup_permutation_dev.  As eon_quotient_values_lk_dev: pre_trace
+ * must be non-NULL exactly when the program has preprocessed columns (the reference takes
+ * air.preprocessed_trace(), :39) and perm_trace exactly when it has permutation columns (:25; both
+ * EON_E_ARG otherwise); n_public (:27) and n_challenges (:26) must be the program's (EON_E_SHAPE);
+ * a public value or challenge that is not canonical is EON_E_ARG; height (:38) must be a power of
+ * two in [1, 2^28] (EON_E_SHAPE; height 1 wraps next onto the row itself, :42); a program created
+ * on another context is EON_E_ARG.  A program with zero constraints reports failures = 0.  The
+ * register file follows eon_quotient_values_lk_dev's rule (LDS, or global for very large programs
+ * and with EON_AIR_REGS=global). */
+int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* trace,
+                              const eon_fr* pre_trace, const eon_fr* perm_trace, uint64_t height,
+                              const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
+                              uint32_t n_challenges, uint32_t* per_constraint, eon_constraint_report* out);
 
 /* out[i] = sum_{j<k} coeffs[j] * in[j * rows + i] (device in/out, host coeffs, 1 <= k <= 64):
  * the combine step of the lane-sharded quotient -- every rank all-gathers the

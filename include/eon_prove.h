@@ -43,6 +43,32 @@ void eon_kzg_pcs_destroy(eon_kzg_pcs* pcs);
 /* message of the last failing call on this pcs (driver-side errors and eon.h errors) */
 const char* eon_kzg_pcs_last_error(const eon_kzg_pcs* pcs);
 
+/* ---- check_constraints in the prove (eon-uni-stark/src/prover.rs:252-262) -----------------------
+ * The reference runs check_constraints (check_constraints.rs:22-101) in every debug build, right
+ * after the permutation trace is generated and before alpha is sampled.  This switch is that
+ * cfg(debug_assertions): off by default, and with it off every prove is byte for byte and launch
+ * for launch what it is without this surface.  With it on, eon_prove_air, _pp and _lk (fixed
+ * challenges and _fs alike) run eon_check_constraints_dev at that point -- after
+ * generate_permutation, before the permutation commitment and alpha -- on the trace, the
+ * preprocessed trace (pre_trace of the _lk forms when given; otherwise the device copy of the
+ * matrix that eon_setup_preprocessed already keeps next to its coefficients, so nothing is
+ * recomputed), the device permutation trace and the permutation challenges.  Its time is counted
+ * in EON_STAGE_TRACE_LDE.  On a failing constraint the prove returns EON_E_CONSTRAINT (eon.h),
+ * eon_kzg_pcs_last_error reads
+ *   "Constraint failed at row R: constraint K of N, expected zero, got 0x<canonical value, 64 hex>"
+ * (the reference's panic, check_constraints.rs:165-173, plus the constraint), no field of the proof
+ * is written, and in the _fs forms the challenger is left as advanced so far: log_ext_degree,
+ * log_degree, the preprocessed width, the trace and preprocessed commitments and the public values
+ * observed, the permutation challenges sampled; the permutation commitment is not observed and alpha
+ * is not sampled.  eon_kzg_pcs_last_constraint_report copies the report of the last eon_prove_air*
+ * call that ran with the switch on (failures == 0 when it passed, or when the prove failed before
+ * the check).  eon_prove_p2air[_fs] (the fused kernel) has no program and ignores the switch: check
+ * a Poseidon2 trace by compiling the same AIR into an eon_air_program (AirProgram(Poseidon2Air))
+ * and calling eon_check_constraints_dev or eon_prove_air. */
+int eon_kzg_pcs_set_check_constraints(eon_kzg_pcs* pcs, int enable);
+int eon_kzg_pcs_check_constraints(const eon_kzg_pcs* pcs); /* 1 / 0 */
+int eon_kzg_pcs_last_constraint_report(const eon_kzg_pcs* pcs, eon_constraint_report* out);
+
 /* Lane-sharded prove: this rank's share of VECTOR_LEN and an all-gather over
  * DEVICE buffers (eon_collective, declared in eon.h). */
 
@@ -237,7 +263,7 @@ int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
                         eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out);
 
 /* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
- * surface above; both additive) */
+ * surface above; 6: the check_constraints switch and report; all additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

@@ -18,12 +18,13 @@ EON_E_DEGREE_TOO_LARGE = -2
 EON_E_DEVICE = -3
 EON_E_OOM = -4
 EON_E_ARG = -5
+EON_E_CONSTRAINT = -6
 EON_ORDER_NATURAL = 0
 EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 8  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 9  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -31,6 +32,7 @@ _ERRNAMES = {
     EON_E_DEVICE: "EON_E_DEVICE",
     EON_E_OOM: "EON_E_OOM",
     EON_E_ARG: "EON_E_ARG",
+    EON_E_CONSTRAINT: "EON_E_CONSTRAINT",
 }
 
 
@@ -67,6 +69,11 @@ class eon_air_program_stats(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("width", "num_public_values", "num_constraints",
                                                "max_constraint_degree", "num_instructions", "num_registers",
                                                "num_constants")]
+
+
+class eon_constraint_report(ctypes.Structure):
+    _fields_ = [("failures", ctypes.c_uint64), ("row", ctypes.c_uint64), ("constraint", ctypes.c_uint32),
+                ("failing_constraints", ctypes.c_uint32), ("value", eon_fr)]
 
 
 class eon_clock_probe(ctypes.Structure):
@@ -172,6 +179,7 @@ SIGNATURES = {
     "eon_quotient_values_pp_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     "eon_quotient_values_lk_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P, _U32, _P]),
     "eon_lookup_permutation_dev": (_INT, [_P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P]),
+    "eon_check_constraints_dev": (_INT, [_P, _P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P, _P]),
     "eon_fr_lincomb_dev": (_INT, [_P, _P, _U32, _U64, _P, _P]),
     "eon_fourstep_twiddle_pack_dev": (_INT, [_P, _P, _U32, _U32, _U64, _U32, _U32, _P]),
 }

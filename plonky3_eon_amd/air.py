@@ -12,6 +12,7 @@ Device matrices are torch CUDA int64 tensors of shape (rows, cols, 4) (Fr Montgo
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 
@@ -143,6 +144,28 @@ class Poseidon2Air:
                 s, k = full(s, rc, k)
 
 
+@dataclasses.dataclass
+class ConstraintReport:
+    """eon_constraint_report (include/eon.h): what check_constraints found.  `row`, `constraint`
+    and `value` (canonical int) describe the reference's first failure and are zero when
+    `failures` is; `counts[k]` = rows on which constraint k fails (when asked for)."""
+
+    failures: int
+    row: int
+    constraint: int
+    value: int
+    failing_constraints: int
+    counts: list | None = None
+
+    @classmethod
+    def from_abi(cls, rep, counts=None) -> "ConstraintReport":
+        from .field import fr_unmont
+
+        v = sum(int(x) << (64 * i) for i, x in enumerate(rep.value.l))
+        return cls(int(rep.failures), int(rep.row), int(rep.constraint), fr_unmont(v),
+                   int(rep.failing_constraints), counts)
+
+
 class AirProgram:
     """An AIR compiled for the generic quotient path (eon_air_program, include/eon.h): the
     constraint DAG get_symbolic_constraints returns (symbolic.py) -> device program.
@@ -239,6 +262,38 @@ class AirProgram:
             pub.ctypes.data_as(ctypes.c_void_p), len(publics), ch.ctypes.data_as(ctypes.c_void_p), len(challenges),
             _dp(out)))
         return out
+
+    def check_constraints(self, trace, publics=(), preprocessed_trace=None, permutation_trace=None, challenges=(),
+                          per_constraint: bool = False) -> "ConstraintReport":
+        """check_constraints (eon-uni-stark/src/check_constraints.rs:22-101) on the device: every row
+        of `trace` (N, width, 4) with its successor (wrapping), `preprocessed_trace` (N,
+        preprocessed_width, 4) and `permutation_trace` (N, permutation_width, 4) on the same trace
+        domain, the 0 / 1 row selectors, `publics` and `challenges` as canonical ints.  Returns the
+        reference's first failure (lowest row, then lowest constraint in assert order) with its
+        value, and the counts; `per_constraint`: also the rows on which each constraint fails."""
+        import torch
+
+        n = int(trace.shape[0])
+        mats = []
+        for name, m, w in (("preprocessed_trace", preprocessed_trace, self.preprocessed_width),
+                           ("permutation_trace", permutation_trace, self.permutation_width)):
+            if m is not None:
+                m = m.contiguous()
+                if m.device != trace.device or tuple(m.shape) != (n, w, 4):
+                    raise ValueError(f"{name} must be ({n}, {w}, 4) on {trace.device}")
+            mats.append(m)
+        pub = _publics_limbs(publics)
+        ch = _publics_limbs(challenges)
+        counts = np.zeros(max(1, self.num_constraints), np.uint32) if per_constraint else None
+        rep = _lib.eon_constraint_report()
+        self.ctx.set_stream(torch.cuda.current_stream(trace.device).cuda_stream)
+        self.ctx.check(self.ctx.lib.eon_check_constraints_dev(
+            self.ctx.handle, self._h, _dp(trace.contiguous()), _dp(mats[0]) if mats[0] is not None else None,
+            _dp(mats[1]) if mats[1] is not None else None, n, pub.ctypes.data_as(ctypes.c_void_p), len(publics),
+            ch.ctypes.data_as(ctypes.c_void_p), len(challenges),
+            counts.ctypes.data_as(ctypes.c_void_p) if counts is not None else None, ctypes.byref(rep)))
+        return ConstraintReport.from_abi(rep, [int(c) for c in counts[:self.num_constraints]]
+                                         if counts is not None else None)
 
     def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=(), preprocessed_lde=None,
                         permutation_lde=None, challenges=()):

@@ -26,6 +26,11 @@
 // trip).  Arithmetic is radix 2^29 with compiler-tracked value bounds (below).  Registers 0 and 1
 // live in VGPRs, the rest in LDS (three planes: two 16-byte, one 4-byte; conflict-free accesses)
 // sized by the program's register count, or in a global buffer for very large programs.
+//
+// The same program runs two more ways, both on the TRACE domain (local = row i, next = row (i + 1)
+// mod height): k_lookup_terms emits the lookups' denominators and multiplicities, and k_air_check
+// is check_constraints (eon-uni-stark/src/check_constraints.rs:22-101): 0 / 1 row selectors and
+// every ASSERT tested for zero mod p, reduced to the first failure and the counts.
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -147,7 +152,7 @@ struct MemRegs {
 // likewise when absent.
 template <bool PRE, bool PERM = false>
 struct Window {
-    static constexpr bool has_pre = PRE, has_perm = PERM, terms = false;
+    static constexpr bool has_pre = PRE, has_perm = PERM, terms = false, check = false;
     const Fr* local;
     const Fr* next;
     const Fr* pre_local;  // the preprocessed matrix's row pair (PRE only)
@@ -210,6 +215,17 @@ __device__ __forceinline__ F29 fetch(uint32_t opnd, const RF& rf, const F29& pre
         if (hot_get(hot, i, x)) return x;
         return rf.get(i - AIR_VREGS);
     }
+    if constexpr (Win::check) {
+        // the trace-domain selectors are the field elements 1 / 0 (check_constraints.rs:88-90),
+        // synthesised from the row: no table, no load
+        if (m >= M_FIRST) {
+            const bool one = m == M_FIRST ? w.row == 0 : m == M_LAST ? w.row + 1 == w.q : w.row + 1 != w.q;
+            F29 s;
+#pragma unroll
+            for (int k = 0; k < 9; k++) s.l[k] = one ? R29<FrP>::ONE[k] : 0u;
+            return s;
+        }
+    }
     // local / next row cell (of the main or the preprocessed matrix: the index is uniform, so
     // which one is a scalar compare) or a selector: the address picked by the (uniform) mode, one
     // load
@@ -255,7 +271,12 @@ __device__ __forceinline__ void exec1(const Instr& in, RF& rf, const Win& w, con
             return;
         }
     }
-    if (opc == OP_ASSERT) {  // folder.rs:81-85, alpha powers reversed
+    if constexpr (Win::check) {  // check_constraints: an ASSERT is tested for zero mod p, not folded
+        if (opc == OP_ASSERT) {
+            w.test(x);
+            return;
+        }
+    } else if (opc == OP_ASSERT) {  // folder.rs:81-85, alpha powers reversed
         const uint32_t kind = in.op >> K_SHIFT;
         if (kind == AS_PAIR)  // acc < 34p, pend < 32p: acc alpha^2 + pend alpha < 132 p^2
             acc = add29_lazy(mul29_sum2_u<FrP>(alpha2, acc, alpha, pend), x);
@@ -378,7 +399,7 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
 // rows, so a wave's stores are contiguous.  lookup.hip brings them to canonical form.
 template <bool PRE>
 struct TermWindow {
-    static constexpr bool has_pre = PRE, has_perm = false, terms = true;
+    static constexpr bool has_pre = PRE, has_perm = false, terms = true, check = false;
     const Fr* local;
     const Fr* next;
     const Fr* pre_local;
@@ -434,6 +455,128 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_lookup_terms(const CodeBlock* __r
     run_program(code, n_blocks, rf, w, zero, acc);
 }
 
+// ---- check_constraints (eon-uni-stark/src/check_constraints.rs:22-101) ------------------------------
+// The third way to run the program: on the TRACE domain (local = row i, next = row (i + 1) mod
+// height, all three matrices), with the 0 / 1 row selectors (:88-90), every ASSERT tested for zero
+// mod p in assert order (the reference's assert_zero, :182-190) instead of folded.
+//
+// The program counter is uniform, so the k-th ASSERT is reached by every lane at once and k is a
+// uniform counter (the schedule emits the ASSERTs in constraint order).  Per ASSERT the fail flags
+// are one ballot: its popcount goes to per_constraint[k] (one global vector atomic of lane 0, only
+// when nonzero) and to the wave's total (uniform arithmetic: the sum of the lanes' own counts);
+// each lane keeps its first failing k by a select.  After the program the lowest lane with a
+// failure -- the wave's lowest row, so its lowest key row * num_constraints + k -- does one 64-bit
+// atomic min, and lane 0 one 64-bit atomic add of the total.  No per-lane atomics, no branch on a
+// lane's fail flag; lanes past the last row have returned and take part in no ballot.
+//
+// With `target` set (the second launch: one thread on the first failing row) nothing is counted and
+// ASSERT `target`'s operand is stored as a canonical Fr in ABI form.
+constexpr uint32_t NO_FAIL = ~0u;
+struct CheckState {
+    uint32_t k = 0;            // ordinal of the next ASSERT (uniform)
+    uint32_t first = NO_FAIL;  // this lane's first failing constraint
+    uint64_t total = 0;        // the wave's failures so far (uniform)
+};
+template <bool PRE, bool PERM>
+struct CheckWindow {
+    static constexpr bool has_pre = PRE, has_perm = PERM, terms = false, check = true;
+    const Fr* local;
+    const Fr* next;
+    const Fr* pre_local;
+    const Fr* pre_next;
+    const Fr* perm_local;
+    const Fr* perm_next;
+    uint32_t width;
+    uint32_t perm_base;
+    const F29* table;  // program constants, public values, challenges
+    const Fr* sels;    // never read (the selectors are synthesised in fetch); a valid address
+    uint64_t row, q;   // q = the trace height
+    uint32_t target;   // NO_FAIL: count failures; else store that ASSERT's value
+    uint32_t* per_constraint;
+    Fr* value_out;
+    mutable CheckState st;
+    // x: the interpreter's lazy form (x 2^261, normalised limbs, < B_RAW p < 2^261).  reduce_top29
+    // brings it below 2p, where zero mod p is {0, p}: a nonzero multiple of p is zero.
+    __device__ __forceinline__ void test(const F29& x) const {
+        const F29 r = reduce_top29<FrP>(x);
+        const uint32_t k = st.k;
+        st.k = k + 1;
+        if (target != NO_FAIL) {  // uniform
+            if (k == target)  // x 2^261 * 2^256 2^-261 = x 2^256, the ABI form
+                st_vec(value_out, pack29<FrP>(canon29<FrP>(mul29<FrP>(r, const29<FrP>(R29<FrP>::TO256)))));
+            return;
+        }
+        const bool fail = !is_zero_mod29<FrP>(r);
+        const uint64_t mask = __ballot(fail);
+        if (mask != 0) {  // uniform
+            const uint32_t n = (uint32_t)__popcll(mask);
+            st.total += n;
+            if ((threadIdx.x & 63) == 0) atomicAdd(per_constraint + k, n);
+        }
+        st.first = (fail && st.first == NO_FAIL) ? k : st.first;
+    }
+};
+
+// One thread per trace row row0 + t, t < n_rows (the check: row0 = 0, n_rows = height; the value
+// launch: row0 = the failing row, n_rows = 1).  summary[0]: min key, summary[1]: failures.
+// A partial wave exists only when n_rows < 64 (heights are powers of two): its live lanes are the
+// low ones, so lane 0 is live in every wave that runs.
+template <int MODE, bool PRE, bool PERM>
+__global__ void __launch_bounds__(AIR_BLOCK) k_air_check(const CodeBlock* __restrict__ code, uint32_t n_blocks,
+                                                     uint32_t n_regs, const Fr* __restrict__ trace, uint32_t width,
+                                                     const Fr* __restrict__ pre, uint32_t pre_width,
+                                                     const Fr* __restrict__ perm, uint32_t perm_width,
+                                                     uint64_t height, const F29* __restrict__ table, uint64_t row0,
+                                                     uint64_t n_rows, uint32_t target, uint32_t n_constraints,
+                                                     uint32_t* __restrict__ per_constraint,
+                                                     unsigned long long* __restrict__ summary,
+                                                     Fr* __restrict__ value_out, uint4* __restrict__ gregs) {
+    extern __shared__ uint4 lds_regs[];
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_rows) return;
+    const uint64_t row = row0 + t;
+    const uint64_t next_row = row + 1 == height ? 0 : row + 1;
+    CheckWindow<PRE, PERM> w{trace + row * width,
+                             trace + next_row * width,
+                             PRE ? pre + row * pre_width : nullptr,
+                             PRE ? pre + next_row * pre_width : nullptr,
+                             PERM ? perm + row * perm_width : nullptr,
+                             PERM ? perm + next_row * perm_width : nullptr,
+                             width,
+                             PERM ? width + pre_width : 0,
+                             table,
+                             trace,
+                             row,
+                             height,
+                             target,
+                             per_constraint,
+                             value_out,
+                             CheckState{}};
+    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
+    MemRegs rf;
+    if (MODE == 0) {
+        rf.base = lds_regs + threadIdx.x;
+        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x) + threadIdx.x;
+        rf.stride = blockDim.x;
+    } else {
+        rf.base = gregs + row;
+        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem * height) + row;
+        rf.stride = height;
+    }
+    F29 acc, zero;
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc.l[i] = zero.l[i] = 0;
+    run_program(code, n_blocks, rf, w, zero, acc);
+    if (target != NO_FAIL) return;
+    const uint64_t any = __ballot(w.st.first != NO_FAIL);
+    if (any != 0) {  // uniform
+        const uint32_t lane = threadIdx.x & 63;
+        if (lane == (uint32_t)__ffsll((long long)any) - 1)
+            atomicMin(summary, (unsigned long long)(row * n_constraints + w.st.first));
+        if (lane == 0) atomicAdd(summary + 1, (unsigned long long)w.st.total);
+    }
+}
+
 }  // namespace
 
 struct eon_air_program {
@@ -451,6 +594,7 @@ struct eon_air_program {
     std::vector<Instr> code;
     std::vector<Fr> consts;
     DevBuf d_code, d_table, d_sels, d_regs;
+    DevBuf d_check;  // eon_check_constraints_dev: min key | failures | value | per-constraint counts
     std::vector<Fr> staged;  // host copy of the table for the current launch
     std::vector<F29> staged29;  // the same in the device's form (x 2^261, < 2p)
 };
@@ -460,6 +604,31 @@ namespace {
 int finish(eon_ctx* ctx, const Status& s) {
     if (s.bad()) ctx->last_error = s.msg;
     return s.code;
+}
+
+// The register file of a k_air_quotient / k_air_check launch over `rows` rows: LDS (the block
+// shrinks with the register count), or the program's global buffer for very large programs and
+// with EON_AIR_REGS=global (for tests; read once per process).  MemRegs: 36 bytes per register in
+// memory.
+struct RegFile {
+    uint32_t block = AIR_BLOCK;
+    int mode = 0;  // 0: LDS, 1: global
+    size_t shmem = 0;
+};
+Status plan_regs(eon_air_program* prog, uint64_t rows, RegFile* out) {
+    const uint64_t per_thread = (uint64_t)(prog->n_regs > AIR_VREGS ? prog->n_regs - AIR_VREGS : 0) * 36;
+    static const bool force_global = [] {
+        const char* e = getenv("EON_AIR_REGS");
+        return e && std::string(e) == "global";
+    }();
+    RegFile r;
+    while (r.block > 64 && r.block * per_thread > 64 * 1024) r.block /= 2;
+    r.mode = !force_global && r.block * per_thread <= 160 * 1024 ? 0 : 1;
+    if (r.mode != 0) r.block = AIR_BLOCK;
+    if (r.mode == 1) EON_HIP(prog->d_regs.ensure(std::max<uint64_t>(1, rows * per_thread)));
+    r.shmem = r.mode == 0 ? (size_t)r.block * per_thread : 0;
+    *out = r;
+    return Status::ok();
 }
 
 // the constant table of a launch: program constants ++ public values ++ challenges, in the device's
@@ -488,7 +657,8 @@ Status stage_table(eon_ctx* ctx, eon_air_program* prog, const eon_fr* publics, u
 }
 
 void release_program(eon_air_program* p) {
-    for (DevBuf* b : {&p->d_code, &p->d_table, &p->d_sels, &p->d_regs, &p->d_desc, &p->d_terms, &p->d_flag})
+    for (DevBuf* b : {&p->d_code, &p->d_table, &p->d_sels, &p->d_regs, &p->d_desc, &p->d_terms, &p->d_flag,
+                      &p->d_check})
         b->release();
     if (p->terms) release_program(p->terms.get());
 }
@@ -1028,21 +1198,12 @@ int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
             inv_van = zh_inv;
         }
         const uint32_t nr_mask = prog->uses_sels ? (uint32_t)(q - 1) : (1u << log_qd) - 1;
-        // register file: LDS (block size shrinks with the register count), or global for very large
-        // programs (EON_AIR_REGS=global forces it, for tests)
-        static const bool force_global = [] {
-            const char* e = getenv("EON_AIR_REGS");
-            return e && std::string(e) == "global";
-        }();
-        // MemRegs: 36 bytes per register in memory
-        const uint64_t per_thread = (uint64_t)(prog->n_regs > AIR_VREGS ? prog->n_regs - AIR_VREGS : 0) * 36;
-        uint32_t block = AIR_BLOCK;
-        while (block > 64 && block * per_thread > 64 * 1024) block /= 2;
-        const int mode = !force_global && block * per_thread <= 160 * 1024 ? 0 : 1;
-        if (mode != 0) block = AIR_BLOCK;
-        if (mode == 1) EON_HIP(prog->d_regs.ensure(std::max<uint64_t>(1, q * per_thread)));
+        RegFile regs;
+        EON_TRY(plan_regs(prog, q, &regs));
+        const uint32_t block = regs.block;
+        const int mode = regs.mode;
+        const size_t shmem = regs.shmem;
         const unsigned grid = (unsigned)((q + block - 1) / block);
-        const size_t shmem = mode == 0 ? (size_t)block * per_thread : 0;
         // algorithmic 256-bit products per row: the program's multiplications, one acc * alpha per
         // constraint (ASSERT) and the final inv_vanishing product (additions, subtractions and
         // negations are not products)
@@ -1179,6 +1340,111 @@ int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
                                               std::to_string(prog->aux[flag]) +
                                               "): a denominator alpha - fold(elements, beta) is zero on some row; "
                                               "the permutation trace is not valid");
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* trace,
+                              const eon_fr* pre_trace, const eon_fr* perm_trace, uint64_t height,
+                              const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
+                              uint32_t n_challenges, uint32_t* per_constraint, eon_constraint_report* out) {
+    if (!ctx || !prog_c) return EON_E_ARG;
+    auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (!trace || !out || (n_public && !publics) || (n_challenges && !challenges))
+            return Status::err(EON_E_ARG, "null argument");
+        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+        if ((perm_trace != nullptr) != (prog->perm_width > 0))
+            return Status::err(EON_E_ARG, prog->perm_width > 0
+                                              ? "the program reads permutation columns: perm_trace must not be null"
+                                              : "the program has no permutation columns: perm_trace must be null");
+        if (n_challenges != prog->n_challenges)
+            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
+        if ((pre_trace != nullptr) != (prog->pre_width > 0))
+            return Status::err(EON_E_ARG, prog->pre_width > 0
+                                              ? "the program reads preprocessed columns: pre_trace must not be null"
+                                              : "the program has no preprocessed columns: pre_trace must be null");
+        if (n_public != prog->n_public)
+            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
+        if (height == 0 || (height & (height - 1)) || height > (1ull << 28))
+            return Status::err(EON_E_SHAPE, "trace height must be a power of two <= 2^28");
+        EON_TRY(stage_table(ctx, prog, publics, n_public, challenges, n_challenges));
+        *out = eon_constraint_report{};
+        const uint32_t nc = prog->n_constraints;
+        if (per_constraint) std::fill(per_constraint, per_constraint + nc, 0u);
+        if (nc == 0) return Status::ok();
+        // device results: min key (8) | failures (8) | value (32) | per-constraint counts (4 nc)
+        constexpr size_t HEAD = 16 + sizeof(Fr);
+        EON_HIP(prog->d_check.ensure(HEAD + (size_t)nc * sizeof(uint32_t)));
+        char* res = prog->d_check.as<char>();
+        EON_HIP(hipMemsetAsync(res, 0, HEAD + (size_t)nc * sizeof(uint32_t), ctx->stream));
+        EON_HIP(hipMemsetAsync(res, 0xff, 8, ctx->stream));
+        RegFile regs;  // the quotient's rule
+        EON_TRY(plan_regs(prog, height, &regs));
+        const uint32_t block = regs.block;
+        const int mode = regs.mode;
+        const size_t shmem = regs.shmem;
+        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
+                                  const Fr*, uint32_t, uint64_t, const F29*, uint64_t, uint64_t, uint32_t, uint32_t,
+                                  uint32_t*, unsigned long long*, Fr*, uint4*);
+        const bool has_pre = prog->pre_width > 0, has_perm = prog->perm_width > 0;
+        const KernelFn kern = mode == 0 ? (has_perm  ? k_air_check<0, true, true>
+                                           : has_pre ? k_air_check<0, true, false>
+                                                     : k_air_check<0, false, false>)
+                                        : (has_perm  ? k_air_check<1, true, true>
+                                           : has_pre ? k_air_check<1, true, false>
+                                                     : k_air_check<1, false, false>);
+        if (mode == 0)
+            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        const CodeBlock* code = prog->d_code.as<CodeBlock>();
+        const uint32_t n_blocks = (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK);
+        auto* summary = reinterpret_cast<unsigned long long*>(res);
+        Fr* value = reinterpret_cast<Fr*>(res + 16);
+        uint32_t* counts = reinterpret_cast<uint32_t*>(res + HEAD);
+        auto launch = [&](uint64_t row0, uint64_t n_rows, uint32_t target, uint32_t run_blocks) {
+            hipLaunchKernelGGL(kern, dim3((unsigned)((n_rows + block - 1) / block)), dim3(block), shmem, ctx->stream,
+                               code, run_blocks, prog->n_regs, reinterpret_cast<const Fr*>(trace), prog->width,
+                               reinterpret_cast<const Fr*>(pre_trace), prog->pre_width,
+                               reinterpret_cast<const Fr*>(perm_trace), prog->perm_width, height,
+                               prog->d_table.as<F29>(), row0, n_rows, target, nc, counts, summary, value,
+                               mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
+        };
+        uint64_t products = 0;  // algorithmic 256-bit products per row: no folds, no inv_vanishing
+        for (const Instr& in : prog->code) {
+            const uint32_t opc = in.op & OP_MASK;
+            products += (opc == OP_MUL || opc == OP_SQR) ? 1 : 0;
+        }
+        ctx->prof.begin("k_air_check", height * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32,
+                        ctx->stream, height * products);
+        launch(0, height, NO_FAIL, n_blocks);
+        ctx->prof.end(ctx->stream);
+        EON_HIP(hipGetLastError());
+        std::vector<unsigned long long> head(2);
+        std::vector<uint32_t> host_counts(nc);
+        EON_HIP(hipMemcpyAsync(head.data(), summary, 16, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipMemcpyAsync(host_counts.data(), counts, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        if (per_constraint) std::copy(host_counts.begin(), host_counts.end(), per_constraint);
+        out->failures = head[1];
+        for (const uint32_t c : host_counts) out->failing_constraints += c != 0 ? 1 : 0;
+        if (head[1] == 0) return Status::ok();
+        out->row = head[0] / nc;
+        out->constraint = (uint32_t)(head[0] % nc);
+        // the value: one thread on that row runs the program up to that ASSERT's code block and
+        // stores its operand
+        uint32_t at = 0;
+        for (uint32_t seen = 0; at < prog->code.size(); at++)
+            if ((prog->code[at].op & OP_MASK) == OP_ASSERT && seen++ == out->constraint) break;
+        launch(out->row, 1, out->constraint, at / CODE_BLOCK + 1);
+        EON_HIP(hipGetLastError());
+        static_assert(sizeof(Fr) == sizeof(eon_fr), "Fr is the ABI's 32 little-endian bytes");
+        EON_HIP(hipMemcpyAsync(&out->value, value, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
     }();
     return finish(ctx, s);

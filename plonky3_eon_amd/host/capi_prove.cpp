@@ -10,6 +10,8 @@
 struct eon_kzg_pcs {
     eon_host::KzgPcs* pcs = nullptr;
     std::string last_error;
+    bool check_constraints = false;        // eon_kzg_pcs_set_check_constraints
+    eon_constraint_report last_report{};   // of the last eon_prove_air* that ran with the switch on
 };
 
 struct eon_preprocessed {
@@ -40,6 +42,17 @@ int guarded(eon_kzg_pcs* h, F&& f) {
     }
 }
 
+// a prove of a program: f(check) with the constraint check when the pcs has it switched on; the
+// report is kept on the pcs whether the prove succeeded or not
+template <class F>
+int guarded_prove(eon_kzg_pcs* h, F&& f) {
+    eon_host::ConstraintCheck cc;
+    const bool on = h->check_constraints;
+    const int rc = guarded(h, [&] { f(on ? &cc : nullptr); });
+    if (on) h->last_report = cc.report;
+    return rc;
+}
+
 void copy_out(const eon_host::Proof& p, eon_proof* out);
 void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out);
 void copy_out_lk(const eon_host::Proof& p, eon_proof_lk* out);
@@ -61,7 +74,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 5; }
+uint32_t eon_prove_abi_version(void) { return 6; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -84,6 +97,20 @@ void eon_kzg_pcs_destroy(eon_kzg_pcs* pcs) {
 }
 
 const char* eon_kzg_pcs_last_error(const eon_kzg_pcs* pcs) { return pcs ? pcs->last_error.c_str() : "null pcs"; }
+
+int eon_kzg_pcs_set_check_constraints(eon_kzg_pcs* pcs, int enable) {
+    if (!pcs) return EON_E_ARG;
+    pcs->check_constraints = enable != 0;
+    return EON_OK;
+}
+
+int eon_kzg_pcs_check_constraints(const eon_kzg_pcs* pcs) { return pcs && pcs->check_constraints ? 1 : 0; }
+
+int eon_kzg_pcs_last_constraint_report(const eon_kzg_pcs* pcs, eon_constraint_report* out) {
+    if (!pcs || !out) return EON_E_ARG;
+    *out = pcs->last_report;
+    return EON_OK;
+}
 
 int eon_poseidon2_bn254_permute(const eon_poseidon2_constants* perm, eon_fr state[3]) {
     if (!perm || !state) return EON_E_ARG;
@@ -168,13 +195,14 @@ int eon_prove_air(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* t
     if (!out->trace_commit || !out->quotient_commit || !out->trace_opened || !out->trace_witnesses ||
         !out->quotient_opened || !out->quotient_witnesses)
         return EON_E_ARG;
-    return guarded(pcs, [&] {
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
         using namespace eon_host;
         AirRef a;
         a.prog = prog;
         a.publics = publics;
         a.n_public = n_public;
-        Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr);
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
+                        nullptr, nullptr, cc);
         copy_out(p, out);
     });
 }
@@ -186,13 +214,14 @@ int eon_prove_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
     if (!out->trace_commit || !out->quotient_commit || !out->trace_opened || !out->trace_witnesses ||
         !out->quotient_opened || !out->quotient_witnesses)
         return EON_E_ARG;
-    return guarded(pcs, [&] {
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
         using namespace eon_host;
         AirRef a;
         a.prog = prog;
         a.publics = publics;
         a.n_public = n_public;
-        Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch);
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch, nullptr,
+                        nullptr, cc);
         copy_out(p, out);
         if (alpha_out) *alpha_out = p.alpha.abi();
         if (zeta_out) *zeta_out = p.zeta.abi();
@@ -237,7 +266,7 @@ int eon_prove_air_pp(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
     if (!pcs || !pcs->pcs || !prog || !trace || !alpha || !zeta || !out || (n_public && !publics))
         return EON_E_ARG;
     if (!proof_arrays_ok(&out->base)) return EON_E_ARG;
-    return guarded(pcs, [&] {
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
         using namespace eon_host;
         if (pp && (!out->preprocessed_commit || !out->preprocessed_opened || !out->preprocessed_witnesses))
             throw Error(EON_E_ARG, "null preprocessed output arrays");
@@ -246,7 +275,7 @@ int eon_prove_air_pp(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
         a.publics = publics;
         a.n_public = n_public;
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
-                        pp ? pp->pp.get() : nullptr);
+                        pp ? pp->pp.get() : nullptr, nullptr, cc);
         copy_out_pp(p, out);
     });
 }
@@ -256,7 +285,7 @@ int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
                         eon_challenger* challenger, eon_proof_pp* out, eon_fr* alpha_out, eon_fr* zeta_out) {
     if (!pcs || !pcs->pcs || !prog || !trace || !challenger || !out || (n_public && !publics)) return EON_E_ARG;
     if (!proof_arrays_ok(&out->base)) return EON_E_ARG;
-    return guarded(pcs, [&] {
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
         using namespace eon_host;
         if (pp && (!out->preprocessed_commit || !out->preprocessed_opened || !out->preprocessed_witnesses))
             throw Error(EON_E_ARG, "null preprocessed output arrays");
@@ -265,7 +294,7 @@ int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
         a.publics = publics;
         a.n_public = n_public;
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch,
-                        pp ? pp->pp.get() : nullptr);
+                        pp ? pp->pp.get() : nullptr, nullptr, cc);
         copy_out_pp(p, out);
         if (alpha_out) *alpha_out = p.alpha.abi();
         if (zeta_out) *zeta_out = p.zeta.abi();
@@ -280,7 +309,7 @@ int eon_prove_air_lk(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
         (n_challenges && !challenges))
         return EON_E_ARG;
     if (!proof_arrays_ok(&out->pp.base)) return EON_E_ARG;
-    return guarded(pcs, [&] {
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
         using namespace eon_host;
         check_lk_arrays(prog, pp != nullptr, out);
         if (n_challenges != eon_air_program_num_challenges(prog))
@@ -293,7 +322,7 @@ int eon_prove_air_lk(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
         lk.pre_trace = pre_trace;
         lk.challenges = challenges;
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
-                        pp ? pp->pp.get() : nullptr, &lk);
+                        pp ? pp->pp.get() : nullptr, &lk, cc);
         copy_out_lk(p, out);
     });
 }
@@ -304,7 +333,7 @@ int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
                         eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out) {
     if (!pcs || !pcs->pcs || !prog || !trace || !challenger || !out || (n_public && !publics)) return EON_E_ARG;
     if (!proof_arrays_ok(&out->pp.base)) return EON_E_ARG;
-    return guarded(pcs, [&] {
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
         using namespace eon_host;
         check_lk_arrays(prog, pp != nullptr, out);
         AirRef a;
@@ -314,7 +343,7 @@ int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
         LookupInputs lk;
         lk.pre_trace = pre_trace;
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch,
-                        pp ? pp->pp.get() : nullptr, &lk);
+                        pp ? pp->pp.get() : nullptr, &lk, cc);
         copy_out_lk(p, out);
         if (challenges_out)
             for (size_t i = 0; i < p.perm_challenges.size(); i++) challenges_out[i] = p.perm_challenges[i].abi();

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -84,7 +85,8 @@ std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_
 
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha_in,
             const Fr& zeta_in, uint32_t max_constraint_degree, const eon_collective* shard,
-            DuplexChallenger* challenger, const Preprocessed* pp, const LookupInputs* lookups) {
+            DuplexChallenger* challenger, const Preprocessed* pp, const LookupInputs* lookups,
+            ConstraintCheck* constraint_check) {
     eon_ctx* ctx = pcs.ctx();
     using clock = std::chrono::steady_clock;
     auto tick = [&] {
@@ -98,6 +100,7 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     if ((air.p2 == nullptr) == (air.prog == nullptr)) throw Error(EON_E_ARG, "exactly one of p2air / program");
     if (air.n_public && !air.publics) throw Error(EON_E_ARG, "null public values");
     if (air.p2 && air.n_public) throw Error(EON_E_SHAPE, "the Poseidon2-AIR has no public values");
+    if (air.p2) constraint_check = nullptr;  // the fused path has no program to check
     const uint32_t width = air.width();
     const uint32_t local_vl = air.p2 ? eon_p2air_vector_len(air.p2) : 1;
     const uint32_t k_lane = air.p2 ? eon_p2air_constraints_per_perm(air.p2) : 0;
@@ -189,8 +192,8 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
                 challenger->observe(Fr::from_abi(air.publics[i]));
             if (perm_width > 0)  // prover.rs:214-216; alpha follows the permutation commitment
                 for (uint32_t i = 0; i < n_challenges; i++) perm_challenges[i] = challenger->sample();
-            else
-                alpha = challenger->sample();
+            else if (!constraint_check)
+                alpha = challenger->sample();  // with the check on, after it (below)
         });
     }
     // the trace LDE (prover.rs:315) while the host thread runs the transcript up to alpha
@@ -203,6 +206,33 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         throw;
     }
     if (fs_thread.joinable()) fs_thread.join();
+    // check_constraints where the reference runs it (prover.rs:252-262): after generate_permutation,
+    // before the permutation commitment and alpha.  The preprocessed trace is the caller's
+    // (pre_trace of the lookup forms), else the evaluations the setup keeps.
+    auto run_check = [&](const eon_fr* perm_trace, const std::vector<eon_fr>& ch) {
+        const eon_fr* pre = lookups && lookups->pre_trace ? lookups->pre_trace
+                            : pp                           ? pp->data.at(0).evals.data()
+                                                           : nullptr;
+        eon_constraint_report& r = constraint_check->report;
+        check(ctx,
+              eon_check_constraints_dev(ctx, air.prog, trace, pre, perm_trace, height, air.publics, air.n_public,
+                                        ch.data(), n_challenges, nullptr, &r),
+              "check_constraints");
+        if (r.failures == 0) return;
+        eon_air_program_stats stats{};
+        (void)eon_air_program_info(air.prog, &stats);
+        const Fr v = fr_mul(Fr::from_abi(r.value), Fr{{1, 0, 0, 0}});  // out of the Montgomery form
+        char hex[2 + 64 + 1];
+        std::snprintf(hex, sizeof(hex), "0x%016llx%016llx%016llx%016llx", (unsigned long long)v.l[3],
+                      (unsigned long long)v.l[2], (unsigned long long)v.l[1], (unsigned long long)v.l[0]);
+        throw Error(EON_E_CONSTRAINT, "Constraint failed at row " + std::to_string(r.row) + ": constraint " +
+                                          std::to_string(r.constraint) + " of " +
+                                          std::to_string(stats.num_constraints) + ", expected zero, got " + hex);
+    };
+    if (constraint_check && perm_width == 0) {
+        run_check(nullptr, {});
+        if (challenger) alpha = challenger->sample();  // prover.rs:300
+    }
     if (perm_width > 0) {
         // generate_permutation (prover.rs:238-245), commit on the trace domain (:270), observe
         // (:273), alpha (:300), then the permutation trace on the quotient domain (:317-319)
@@ -213,6 +243,7 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
               eon_lookup_permutation_dev(ctx, air.prog, trace, lookups->pre_trace, height, air.publics, air.n_public,
                                          ch.data(), n_challenges, perm.mutable_data()),
               "generate_permutation");
+        if (constraint_check) run_check(perm.data(), ch);
         std::vector<std::pair<Domain, DeviceMatrix>> ev;
         ev.emplace_back(trace_domain, std::move(perm));
         pcs.commit(std::move(ev), perm_commit, perm_data);

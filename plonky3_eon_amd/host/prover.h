@@ -60,6 +60,14 @@ struct Preprocessed {
 std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_trace, uint64_t height,
                                                  uint32_t width);
 
+// The constraint check of the reference's debug builds (prover.rs:252-262, check_constraints.rs):
+// when a prove is given one, eon_check_constraints_dev runs on the trace, the preprocessed trace,
+// the permutation trace and the challenges after the permutation trace is generated and before
+// alpha is sampled; `report` is filled either way, and a failure throws EON_E_CONSTRAINT.
+struct ConstraintCheck {
+    eon_constraint_report report{};
+};
+
 // The AIR being proved: the fused Poseidon2-AIR kernel (lane-shardable), or a generic constraint
 // program compiled from get_symbolic_constraints (eon_air_program) with its public values.
 struct AirRef {
@@ -81,10 +89,11 @@ struct AirRef {
 // 2 Wq challenges are sampled after the public values (:214-216), generate_permutation runs on the
 // device (:238-245), its trace is committed on the trace domain and observed (:270-273) before
 // alpha (:300), extended next to the trace (:317-319) and opened at {zeta, zeta h} in the round
-// after the trace's (:427-437).
+// after the trace's (:427-437).  `check` (programs only; null = off, the prove is then launch for
+// launch what it is without it): see ConstraintCheck; its time is counted in EON_STAGE_TRACE_LDE.
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha,
             const Fr& zeta, uint32_t max_constraint_degree, const eon_collective* shard,
             DuplexChallenger* challenger = nullptr, const Preprocessed* preprocessed = nullptr,
-            const LookupInputs* lookups = nullptr);
+            const LookupInputs* lookups = nullptr, ConstraintCheck* check = nullptr);
 
 }  // namespace eon_host

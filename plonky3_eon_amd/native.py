@@ -58,6 +58,9 @@ SIGNATURES = {
     "eon_kzg_pcs_create": (_INT, [_P, _U64, _P, ctypes.POINTER(_P)]),
     "eon_kzg_pcs_destroy": (None, [_P]),
     "eon_kzg_pcs_last_error": (ctypes.c_char_p, [_P]),
+    "eon_kzg_pcs_set_check_constraints": (_INT, [_P, _INT]),
+    "eon_kzg_pcs_check_constraints": (_INT, [_P]),
+    "eon_kzg_pcs_last_constraint_report": (_INT, [_P, ctypes.POINTER(_lib.eon_constraint_report)]),
     "eon_rccl_unique_id": (_INT, [_P]),
     "eon_rccl_collective_init": (_INT, [_U32, _U32, _P, ctypes.POINTER(eon_collective)]),
     "eon_rccl_collective_info": (_INT, [ctypes.POINTER(eon_collective), ctypes.POINTER(ctypes.c_int32),
@@ -110,6 +113,16 @@ def load() -> ctypes.CDLL:
     return lib
 
 
+class ConstraintError(RuntimeError):
+    """EON_E_CONSTRAINT from a prove with NativeKzgPcs.check_constraints on: the trace does not
+    satisfy the AIR.  `report` (air.ConstraintReport) is the first failure and the counts."""
+
+    def __init__(self, msg: str, report):
+        super().__init__(msg)
+        self.code = _lib.EON_E_CONSTRAINT
+        self.report = report
+
+
 class NativeKzgPcs:
     """KzgPcs::new(max_degree, alpha) inside the native driver (SRS and bases on device)."""
 
@@ -123,8 +136,29 @@ class NativeKzgPcs:
         self._h = h
 
     def check(self, rc: int):
+        if rc == _lib.EON_E_CONSTRAINT:
+            raise ConstraintError(self.lib.eon_kzg_pcs_last_error(self._h).decode(), self.last_constraint_report())
         if rc != 0:
             raise _lib.EonError(rc, self.lib.eon_kzg_pcs_last_error(self._h).decode())
+
+    @property
+    def check_constraints(self) -> bool:
+        """Run check_constraints (prover.rs:252-262, the reference's debug builds) in every generic
+        prove; a failing trace then raises ConstraintError instead of yielding a proof."""
+        return bool(self.lib.eon_kzg_pcs_check_constraints(self._h))
+
+    @check_constraints.setter
+    def check_constraints(self, enable: bool):
+        _check(self.lib.eon_kzg_pcs_set_check_constraints(self._h, 1 if enable else 0),
+               "eon_kzg_pcs_set_check_constraints")
+
+    def last_constraint_report(self):
+        from .air import ConstraintReport
+
+        rep = _lib.eon_constraint_report()
+        _check(self.lib.eon_kzg_pcs_last_constraint_report(self._h, ctypes.byref(rep)),
+               "eon_kzg_pcs_last_constraint_report")
+        return ConstraintReport.from_abi(rep)
 
     def close(self):
         if getattr(self, "_h", None):
