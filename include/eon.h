@@ -246,6 +246,7 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   10: eon_air_eval_at_point_dev, the compiled constraints at one out-of-domain point, additive;
  *   9: eon_check_constraints_dev and eon_constraint_report, EON_E_CONSTRAINT, additive;
  *   8: eon_diag_ec29_op, the curve formulas of the MSM bucket sums one per thread, additive;
  *   7: the eon_diag_* stage diagnostics of the MSM digit pipeline and eon_msm_batch_info, additive;
@@ -599,6 +600,33 @@ int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog, const e
                               const eon_fr* pre_trace, const eon_fr* perm_trace, uint64_t height,
                               const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
                               uint32_t n_challenges, uint32_t* per_constraint, eon_constraint_report* out);
+
+/* The constraints at ONE out-of-domain point: the evaluation of verify_constraints
+ * (eon-uni-stark/src/verifier.rs:101-152), the only part of the verifier that needs the AIR.  The
+ * program runs once on opened values: `local` / `next` = width Fr each (the trace at zeta and
+ * zeta h), `pre_local` / `pre_next` = preprocessed_width Fr each, `perm_local` / `perm_next` =
+ * permutation_width Fr each -- six separate DEVICE arrays of canonical Fr, not rows of one matrix.
+ * The selectors are selectors_at_point(zeta) of the trace domain of size 2^log_n
+ * (commit/src/domain.rs:237-246): with Z_H = zeta^N - 1 and h the domain's generator,
+ * is_first_row = Z_H / (zeta - 1), is_last_row = Z_H / (zeta - h^-1), is_transition = zeta - h^-1,
+ * inv_vanishing = 1 / Z_H, computed exactly on the host.  Every constraint -- the AIR's, then the
+ * lookups', in assert order -- is folded as acc = acc alpha + C (folder.rs:188-190).
+ *   out[0] (host) = the folded accumulator, out[1] = folded * inv_vanishing -- the side the verifier
+ *   compares with quotient(zeta); both canonical, ABI form.  A program with zero constraints gives 0.
+ * `zeta`, `alpha`, `publics`, `challenges` are host pointers.  Synchronous, like
+ * eon_check_constraints_dev.  pre_* must be non-NULL exactly when the program has preprocessed
+ * columns and perm_* exactly when it has permutation columns (EON_E_ARG); n_public and n_challenges
+ * must be the program's (EON_E_SHAPE); a zeta, alpha, public value or challenge that is not canonical
+ * is EON_E_ARG; log_n > 28 is EON_E_SHAPE; a program created on another context is EON_E_ARG.  Where
+ * the reference panics on the inverse of zero -- zeta = 1, zeta = h^-1 or Z_H(zeta) = 0 -- the call
+ * returns EON_E_ARG.  One lane runs the program (a latency-bound dependent chain); the register file
+ * follows eon_quotient_values_lk_dev's rule (LDS, or global for very large programs and with
+ * EON_AIR_REGS=global). */
+int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog, uint32_t log_n, const eon_fr* zeta,
+                              const eon_fr* alpha, const eon_fr* local, const eon_fr* next, const eon_fr* pre_local,
+                              const eon_fr* pre_next, const eon_fr* perm_local, const eon_fr* perm_next,
+                              const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
+                              uint32_t n_challenges, eon_fr* out);
 
 /* out[i] = sum_{j<k} coeffs[j] * in[j * rows + i] (device in/out, host coeffs, 1 <= k <= 64):
  * the combine step of the lane-sharded quotient -- every rank all-gathers the

@@ -18,6 +18,8 @@
  *                    branch of prove_with_preprocessed (prover.rs:58-88, 190-208, 321-322, 431)
  *   eon_prove_air_lk the Some(permutation) branch (prover.rs:210-278, 317-319, 427-437): local LogUp
  *                    lookups, the permutation trace generated on the device
+ *   eon_verify_air   verify_with_preprocessed (eon-uni-stark/src/verifier.rs:244-502) for a proof of
+ *                    any of the above: the verdict is the reference's Ok or VerificationError variant
  *   eon_challenger   DuplexChallenger<Fr, Poseidon2Bn254<3>, 3, 2>
  *                    (challenger/src/duplex_challenger.rs, bn254/src/poseidon2.rs) on the host.
  * Conventions are eon.h's: 0 / negative EON_E_* codes (the reference panics), host outputs,
@@ -262,8 +264,61 @@ int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
                         const eon_fr* pre_trace, eon_challenger* challenger, eon_proof_lk* out,
                         eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out);
 
+/* ---- verify (eon-uni-stark/src/verifier.rs:244-502) ----------------------------------------------
+ * verify_with_preprocessed for a proof of ANY eon_prove_* entry, in the reference's order:
+ *   1. shapes: the preprocessed width against the verifier key (process_preprocessed_trace,
+ *      verifier.rs:165-225), the key's degree_bits against the proof's (:272-277), the permutation
+ *      part against the program (:330-352);
+ *   2. the transcript (:355-397): observe degree_bits twice, the preprocessed width, the trace
+ *      commitment, the KEY's preprocessed commitment, the public values; with a permutation
+ *      commitment sample the 2 Wq permutation challenges and observe it; sample alpha, observe the
+ *      quotient commitment, sample zeta;
+ *   3. KzgPcs::verify (kzg/src/pcs.rs:337-401): ensure_supported, then every opening -- trace at
+ *      {zeta, zeta h}, permutation at {zeta, zeta h}, quotient chunks at {zeta}, preprocessed at
+ *      {zeta, zeta h} -- in ONE eon_kzg_verify_batch against g2_alpha = [srs_alpha] G2 (made once per
+ *      pcs with eon_g2_mul);
+ *   4. recompose_quotient_from_chunks (:30-70) on the host;
+ *   5. verify_constraints (:77-160): eon_air_eval_at_point_dev (eon.h) on the opened values, and
+ *      folded * inv_vanishing == quotient(zeta).
+ * A failure of step 3 is reported before step 5 is looked at.
+ *   proof      eon_proof_lk as the superset of the three proof structs: the preprocessed arrays are
+ *              NULL when the proof has no preprocessed part (preprocessed_commit is never read: the
+ *              key's commitment is the one observed and checked), the permutation arrays when it has
+ *              no permutation part.  Array lengths are the program's: W, C = 2^log_quotient_degree,
+ *              Wq, and the key's width (C arrays carry none; a binding checks them, as native.py does).
+ *              A proof of eon_prove_p2air[_fs] is verified with the generic program of the same AIR
+ *              (its constraint order is the fused kernel's).
+ *   vk_*       PreprocessedVerifierKey (preprocessed.rs:30-40) as plain values; vk_commitment NULL =
+ *              no key (vk_width and vk_degree_bits are then ignored)
+ *   challenges, alpha, zeta (eon_verify_air; host) the ones the proof was made with, mirroring
+ *              eon_prove_air_lk; n_challenges must be the program's (EON_E_SHAPE)
+ *   challenger (eon_verify_air_fs) is advanced exactly as the reference's verifier advances its own;
+ *              challenges_out (2 Wq Fr) / alpha_out / zeta_out (host, nullable) receive what it gave
+ *   *result    EON_VERIFY_*: the reference's Ok(()) or its VerificationError variant.  A commitment or
+ *              witness that is no curve point, or an opened value that is no canonical Fr, is
+ *              EON_VERIFY_INVALID_OPENING_ARGUMENT.
+ * The return code is EON_OK whenever the verification ran to a verdict (eon_kzg_pcs_last_error then
+ * says why a proof was rejected); negative codes stay for bad arguments and device errors: a NULL
+ * trace or quotient array, a public value count that is not the program's (EON_E_SHAPE), a zeta on
+ * the trace domain (EON_E_ARG: the reference panics).  ZK (RandomizationError) and global lookups
+ * are outside, as in the prover. */
+enum {
+    EON_VERIFY_OK = 0,
+    EON_VERIFY_INVALID_PROOF_SHAPE = 1,      /* VerificationError::InvalidProofShape */
+    EON_VERIFY_INVALID_OPENING_ARGUMENT = 2, /* VerificationError::InvalidOpeningArgument(KzgError) */
+    EON_VERIFY_OOD_EVALUATION_MISMATCH = 3   /* VerificationError::OodEvaluationMismatch */
+};
+int eon_verify_air(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proof, const eon_fr* publics,
+                   uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits, const eon_g1_affine* vk_commitment,
+                   const eon_fr* challenges, uint32_t n_challenges, const eon_fr* alpha, const eon_fr* zeta,
+                   int* result);
+int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proof,
+                      const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                      const eon_g1_affine* vk_commitment, eon_challenger* challenger, int* result,
+                      eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out);
+
 /* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
- * surface above; 6: the check_constraints switch and report; all additive) */
+ * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; all additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

@@ -12,5 +12,7 @@ There is no CPU fallback: importing an entry point loads libeonhip.so and raises
 from . import _lib  # noqa: F401
 from .dft import Context, Radix2Dit, Radix2DitParallel, BitReversedMatrix, default_context  # noqa: F401
 from ._lib import EonError  # noqa: F401
+from .proof import VerificationError  # noqa: F401  (native.verify_native's rejection)
 
-__all__ = ["Context", "Radix2Dit", "Radix2DitParallel", "BitReversedMatrix", "default_context", "EonError"]
+__all__ = ["Context", "Radix2Dit", "Radix2DitParallel", "BitReversedMatrix", "default_context", "EonError",
+           "VerificationError"]

@@ -295,6 +295,41 @@ class AirProgram:
         return ConstraintReport.from_abi(rep, [int(c) for c in counts[:self.num_constraints]]
                                          if counts is not None else None)
 
+    def eval_at_point(self, log_n: int, zeta, alpha, local, next, publics=(), preprocessed_local=None,
+                      preprocessed_next=None, permutation_local=None, permutation_next=None, challenges=()):
+        """The constraints at one out-of-domain point (verify_constraints, verifier.rs:101-152) on
+        the device: `local` / `next` (width, 4) device tensors of opened values (the trace at zeta and
+        zeta h), the preprocessed and permutation pairs likewise, the selectors
+        selectors_at_point(zeta) of the trace domain of size 2^log_n, every constraint folded as
+        acc = acc alpha + C.  `zeta`, `alpha`, `publics`, `challenges`: canonical ints.  Returns
+        (folded, folded * inv_vanishing) as canonical ints; the second is what the verifier compares
+        with quotient(zeta).  zeta = 1, zeta = h^-1 or Z_H(zeta) = 0 is EON_E_ARG."""
+        import torch
+
+        from .field import fr_unmont
+
+        rows = []
+        for name, m, w in (("local", local, self.width), ("next", next, self.width),
+                           ("preprocessed_local", preprocessed_local, self.preprocessed_width),
+                           ("preprocessed_next", preprocessed_next, self.preprocessed_width),
+                           ("permutation_local", permutation_local, self.permutation_width),
+                           ("permutation_next", permutation_next, self.permutation_width)):
+            if m is not None:
+                m = m.contiguous()
+                if m.device != local.device or tuple(m.shape) != (w, 4):
+                    raise ValueError(f"{name} must be ({w}, 4) on {local.device}")
+            rows.append(m)
+        z, a = fr_to_abi(zeta), fr_to_abi(alpha)
+        pub = _publics_limbs(publics)
+        ch = _publics_limbs(challenges)
+        out = np.zeros((2, 4), np.uint64)
+        self.ctx.set_stream(torch.cuda.current_stream(local.device).cuda_stream)
+        self.ctx.check(self.ctx.lib.eon_air_eval_at_point_dev(
+            self.ctx.handle, self._h, log_n, ctypes.byref(z), ctypes.byref(a),
+            *[_dp(m) if m is not None else None for m in rows], pub.ctypes.data_as(ctypes.c_void_p), len(publics),
+            ch.ctypes.data_as(ctypes.c_void_p), len(challenges), out.ctypes.data_as(ctypes.c_void_p)))
+        return tuple(fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v))) for v in out)
+
     def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=(), preprocessed_lde=None,
                         permutation_lde=None, challenges=()):
         """quotient_values (prover.rs:539-709) on the trace's LDE over GENERATOR * K (natural);

@@ -30,7 +30,9 @@
 // The same program runs two more ways, both on the TRACE domain (local = row i, next = row (i + 1)
 // mod height): k_lookup_terms emits the lookups' denominators and multiplicities, and k_air_check
 // is check_constraints (eon-uni-stark/src/check_constraints.rs:22-101): 0 / 1 row selectors and
-// every ASSERT tested for zero mod p, reduced to the first failure and the counts.
+// every ASSERT tested for zero mod p, reduced to the first failure and the counts.  A fourth way,
+// k_air_point, is the verifier's: one evaluation at an out-of-domain point on opened values, with
+// selectors_at_point instead of coset or 0 / 1 selectors.
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -577,6 +579,63 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_check(const CodeBlock* __rest
     }
 }
 
+// ---- the constraints at one out-of-domain point (verify_constraints, eon-uni-stark/src/verifier.rs:101-152)
+// The fourth way to run the program: ONE evaluation, on opened values instead of matrix rows.  It is
+// the quotient's Window over a one-row "domain" (q = 1, row = 0): local / next (and the preprocessed
+// and permutation pairs) are six separate arrays, the selectors are the three Fr of
+// selectors_at_point(zeta) (commit/src/domain.rs:237-246) computed exactly on the host and read
+// through the same `sels` addressing (mode * q + row), and the folder is the same Horner chain
+// acc = acc alpha + C (folder.rs:188-190).  One lane of one wave is live -- lane 0, as in
+// k_air_check's value launch -- so every readfirstlane in the interpreter reads the live lane; the
+// run is one dependent chain, latency-bound by construction.  out[0] = the folded accumulator,
+// out[1] = folded * inv_vanishing (sels[3]), both canonical in the ABI form.
+template <int MODE, bool PRE, bool PERM>
+__global__ void __launch_bounds__(AIR_BLOCK) k_air_point(const CodeBlock* __restrict__ code, uint32_t n_blocks,
+                                                     uint32_t n_regs, const Fr* __restrict__ local,
+                                                     const Fr* __restrict__ next, const Fr* __restrict__ pre_local,
+                                                     const Fr* __restrict__ pre_next,
+                                                     const Fr* __restrict__ perm_local,
+                                                     const Fr* __restrict__ perm_next, uint32_t width,
+                                                     uint32_t pre_width, const F29* __restrict__ table,
+                                                     const Fr* __restrict__ sels, Fr alpha, Fr* __restrict__ out,
+                                                     uint4* __restrict__ gregs) {
+    extern __shared__ uint4 lds_regs[];
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Window<PRE, PERM> w{local,
+                        next,
+                        PRE ? pre_local : nullptr,
+                        PRE ? pre_next : nullptr,
+                        PERM ? perm_local : nullptr,
+                        PERM ? perm_next : nullptr,
+                        width,
+                        PERM ? width + pre_width : 0,
+                        table,
+                        sels,
+                        0,
+                        1};
+    F29 acc;
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc.l[i] = 0;
+    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
+    MemRegs rf;
+    if (MODE == 0) {
+        rf.base = lds_regs;
+        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x);
+        rf.stride = blockDim.x;
+    } else {  // one row: the planes are contiguous
+        rf.base = gregs;
+        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem);
+        rf.stride = 1;
+    }
+    run_program(code, n_blocks, rf, w, uniform29(shl5_to261<FrP>(alpha)), acc);
+    // acc: x 2^261, < (2 + B_RAW) p, limbs < 2^30.  Times 2^256 (a plain integer < p) it is
+    // x 2^256, the ABI form; times inv_vanishing in the ABI form x y 2^256 (as k_air_quotient)
+    const F29 folded = mul29<FrP>(acc, const29<FrP>(R29<FrP>::TO256));
+    const F29 quot = mul29<FrP>(acc, unpack29(ld_pinned(sels + 3)));
+    st_vec(out, pack29<FrP>(canon29<FrP>(folded)));
+    st_vec(out + 1, pack29<FrP>(canon29<FrP>(quot)));
+}
+
 }  // namespace
 
 struct eon_air_program {
@@ -595,6 +654,7 @@ struct eon_air_program {
     std::vector<Fr> consts;
     DevBuf d_code, d_table, d_sels, d_regs;
     DevBuf d_check;  // eon_check_constraints_dev: min key | failures | value | per-constraint counts
+    DevBuf d_point;  // eon_air_eval_at_point_dev: the four selectors at zeta | the two results
     std::vector<Fr> staged;  // host copy of the table for the current launch
     std::vector<F29> staged29;  // the same in the device's form (x 2^261, < 2p)
 };
@@ -658,7 +718,7 @@ Status stage_table(eon_ctx* ctx, eon_air_program* prog, const eon_fr* publics, u
 
 void release_program(eon_air_program* p) {
     for (DevBuf* b : {&p->d_code, &p->d_table, &p->d_sels, &p->d_regs, &p->d_desc, &p->d_terms, &p->d_flag,
-                      &p->d_check})
+                      &p->d_check, &p->d_point})
         b->release();
     if (p->terms) release_program(p->terms.get());
 }
@@ -1444,6 +1504,97 @@ int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog_c, const
         EON_HIP(hipGetLastError());
         static_assert(sizeof(Fr) == sizeof(eon_fr), "Fr is the ABI's 32 little-endian bytes");
         EON_HIP(hipMemcpyAsync(&out->value, value, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint32_t log_n, const eon_fr* zeta,
+                              const eon_fr* alpha, const eon_fr* local, const eon_fr* next, const eon_fr* pre_local,
+                              const eon_fr* pre_next, const eon_fr* perm_local, const eon_fr* perm_next,
+                              const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
+                              uint32_t n_challenges, eon_fr* out) {
+    if (!ctx || !prog_c) return EON_E_ARG;
+    auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (!zeta || !alpha || !out || (prog->width && (!local || !next)) || (n_public && !publics) ||
+            (n_challenges && !challenges))
+            return Status::err(EON_E_ARG, "null argument");
+        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+        if ((perm_local != nullptr) != (prog->perm_width > 0) || (perm_next != nullptr) != (prog->perm_width > 0))
+            return Status::err(EON_E_ARG, prog->perm_width > 0
+                                              ? "the program reads permutation columns: perm_local and perm_next "
+                                                "must not be null"
+                                              : "the program has no permutation columns: perm_local and perm_next "
+                                                "must be null");
+        if (n_challenges != prog->n_challenges)
+            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
+        if ((pre_local != nullptr) != (prog->pre_width > 0) || (pre_next != nullptr) != (prog->pre_width > 0))
+            return Status::err(EON_E_ARG, prog->pre_width > 0
+                                              ? "the program reads preprocessed columns: pre_local and pre_next "
+                                                "must not be null"
+                                              : "the program has no preprocessed columns: pre_local and pre_next "
+                                                "must be null");
+        if (n_public != prog->n_public)
+            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
+        if (log_n > 28) return Status::err(EON_E_SHAPE, "log_n must be <= 28 (Fr::TWO_ADICITY)");
+        const Fr al = fr_from_abi(alpha), z = fr_from_abi(zeta);
+        if (!fr_is_canonical(al)) return Status::err(EON_E_ARG, "alpha is not a canonical Fr");
+        if (!fr_is_canonical(z)) return Status::err(EON_E_ARG, "zeta is not a canonical Fr");
+        // selectors_at_point of the trace domain (shift 1), commit/src/domain.rs:237-246, exact on the
+        // host: Z_H = zeta^N - 1, is_first_row = Z_H / (zeta - 1), is_last_row = Z_H / (zeta - h^-1),
+        // is_transition = zeta - h^-1, inv_vanishing = 1 / Z_H.  The reference panics (inverse of
+        // zero) where one of the three divisors vanishes.
+        Fr zn = z;
+        for (uint32_t i = 0; i < log_n; i++) zn = sqr(zn);
+        const Fr z_h = sub(zn, Fr::one());
+        const Fr h_inv = inverse(fr_two_adic_generator(log_n));
+        const Fr d_first = sub(z, Fr::one()), d_last = sub(z, h_inv);
+        if (z_h.is_zero() || d_first.is_zero() || d_last.is_zero())
+            return Status::err(EON_E_ARG, "zeta lies on the trace domain: the selectors at zeta are undefined "
+                                          "(the reference's inverse of zero)");
+        const Fr sel_host[4] = {mul(z_h, inverse(d_first)), mul(z_h, inverse(d_last)), d_last, inverse(z_h)};
+        EON_TRY(stage_table(ctx, prog, publics, n_public, challenges, n_challenges));
+        EON_HIP(prog->d_point.ensure(6 * sizeof(Fr)));
+        Fr* sels = prog->d_point.as<Fr>();
+        Fr* res = sels + 4;
+        EON_HIP(hipMemcpyAsync(sels, sel_host, sizeof(sel_host), hipMemcpyHostToDevice, ctx->stream));
+        RegFile regs;  // the quotient's rule, over one row
+        EON_TRY(plan_regs(prog, 1, &regs));
+        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, const Fr*, const Fr*, const Fr*,
+                                  const Fr*, const Fr*, uint32_t, uint32_t, const F29*, const Fr*, Fr, Fr*, uint4*);
+        const bool has_pre = prog->pre_width > 0, has_perm = prog->perm_width > 0;
+        const KernelFn kern = regs.mode == 0 ? (has_perm  ? k_air_point<0, true, true>
+                                                : has_pre ? k_air_point<0, true, false>
+                                                          : k_air_point<0, false, false>)
+                                             : (has_perm  ? k_air_point<1, true, true>
+                                                : has_pre ? k_air_point<1, true, false>
+                                                          : k_air_point<1, false, false>);
+        if (regs.mode == 0)
+            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        uint64_t products = 2;  // algorithmic 256-bit products: the program's, one per fold, the two results
+        for (const Instr& in : prog->code) {
+            const uint32_t opc = in.op & OP_MASK;
+            products += (opc == OP_MUL || opc == OP_SQR || opc == OP_ASSERT) ? 1 : 0;
+        }
+        ctx->prof.begin("k_air_point",
+                        2 * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32 + 6 * 32, ctx->stream,
+                        products);
+        hipLaunchKernelGGL(kern, dim3(1), dim3(regs.block), regs.shmem, ctx->stream, prog->d_code.as<CodeBlock>(),
+                           (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK), prog->n_regs,
+                           reinterpret_cast<const Fr*>(local), reinterpret_cast<const Fr*>(next),
+                           reinterpret_cast<const Fr*>(pre_local), reinterpret_cast<const Fr*>(pre_next),
+                           reinterpret_cast<const Fr*>(perm_local), reinterpret_cast<const Fr*>(perm_next),
+                           prog->width, prog->pre_width, prog->d_table.as<F29>(), sels, al, res,
+                           regs.mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
+        ctx->prof.end(ctx->stream);
+        EON_HIP(hipGetLastError());
+        static_assert(sizeof(Fr) == sizeof(eon_fr), "Fr is the ABI's 32 little-endian bytes");
+        EON_HIP(hipMemcpyAsync(out, res, 2 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
     }();

@@ -6,6 +6,7 @@
 #include "eon_prove.h"
 #include "prover.h"
 #include "transcript.h"
+#include "verifier.h"
 
 struct eon_kzg_pcs {
     eon_host::KzgPcs* pcs = nullptr;
@@ -74,7 +75,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 6; }
+uint32_t eon_prove_abi_version(void) { return 7; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -369,6 +370,65 @@ int eon_prove_p2air_fs(eon_kzg_pcs* pcs, const eon_p2air* air, const eon_fr* tra
         if (alpha_out) *alpha_out = p.alpha.abi();
         if (zeta_out) *zeta_out = p.zeta.abi();
     });
+}
+
+int eon_verify_air(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proof, const eon_fr* publics,
+                   uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits, const eon_g1_affine* vk_commitment,
+                   const eon_fr* challenges, uint32_t n_challenges, const eon_fr* alpha, const eon_fr* zeta,
+                   int* result) {
+    if (!pcs || !pcs->pcs || !prog || !proof || !alpha || !zeta || !result || (n_public && !publics) ||
+        (n_challenges && !challenges))
+        return EON_E_ARG;
+    std::string detail;
+    const int rc = guarded(pcs, [&] {
+        using namespace eon_host;
+        VerifyInputs in;
+        in.prog = prog;
+        in.proof = proof;
+        in.publics = publics;
+        in.n_public = n_public;
+        in.vk_width = vk_width;
+        in.vk_degree_bits = vk_degree_bits;
+        in.vk_commitment = vk_commitment;
+        in.challenges = challenges;
+        in.n_challenges = n_challenges;
+        in.alpha = Fr::from_abi(*alpha);
+        in.zeta = Fr::from_abi(*zeta);
+        const VerifyOutcome o = verify(*pcs->pcs, in, nullptr);
+        *result = o.verdict;
+        detail = o.detail;
+    });
+    if (rc == EON_OK) pcs->last_error = detail;  // why a proof was rejected
+    return rc;
+}
+
+int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proof,
+                      const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                      const eon_g1_affine* vk_commitment, eon_challenger* challenger, int* result,
+                      eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out) {
+    if (!pcs || !pcs->pcs || !prog || !proof || !challenger || !result || (n_public && !publics)) return EON_E_ARG;
+    std::string detail;
+    const int rc = guarded(pcs, [&] {
+        using namespace eon_host;
+        VerifyInputs in;
+        in.prog = prog;
+        in.proof = proof;
+        in.publics = publics;
+        in.n_public = n_public;
+        in.vk_width = vk_width;
+        in.vk_degree_bits = vk_degree_bits;
+        in.vk_commitment = vk_commitment;
+        const VerifyOutcome o = verify(*pcs->pcs, in, &challenger->ch);
+        *result = o.verdict;
+        detail = o.detail;
+        if (o.verdict == EON_VERIFY_INVALID_PROOF_SHAPE) return;  // rejected before the transcript
+        if (challenges_out)
+            for (size_t i = 0; i < o.challenges.size(); i++) challenges_out[i] = o.challenges[i].abi();
+        if (alpha_out) *alpha_out = o.alpha.abi();
+        if (zeta_out) *zeta_out = o.zeta.abi();
+    });
+    if (rc == EON_OK) pcs->last_error = detail;
+    return rc;
 }
 
 }  // extern "C"

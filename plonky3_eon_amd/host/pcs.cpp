@@ -136,7 +136,8 @@ std::vector<Domain> Domain::split_domains(uint32_t num_chunks) const {
     return out;
 }
 
-KzgPcs::KzgPcs(eon_ctx* ctx, uint64_t max_degree, const Fr& srs_alpha) : ctx_(ctx), max_degree_(max_degree) {
+KzgPcs::KzgPcs(eon_ctx* ctx, uint64_t max_degree, const Fr& srs_alpha)
+    : ctx_(ctx), max_degree_(max_degree), srs_alpha_(srs_alpha) {
     // init_srs_unsafe (params.rs:123-139): g1_powers[i] = alpha^i * G for i <= max_degree, made on
     // device and turned into fixed-base MSM bases without a host round trip
     const uint64_t n = max_degree + 1;
@@ -176,6 +177,15 @@ void KzgPcs::ensure_supported(uint64_t degree) const {
     if (degree > max_degree_)
         throw Error(EON_E_DEGREE_TOO_LARGE,
                     "degree " + std::to_string(degree) + " > max " + std::to_string(max_degree_));
+}
+
+const eon_g2_affine& KzgPcs::g2_alpha() {
+    if (!have_g2_alpha_) {
+        const eon_fr a = srs_alpha_.abi();
+        check(ctx_, eon_g2_mul(ctx_, nullptr, &a, &g2_alpha_), "eon_g2_mul");
+        have_g2_alpha_ = true;
+    }
+    return g2_alpha_;
 }
 
 void KzgPcs::commit_coeffs(std::vector<std::pair<Domain, DeviceMatrix>> evaluations,

@@ -139,10 +139,16 @@ class KzgPcs {
     // (eon_kzg_opening_bases_create), reusing the digits sorted at commit time, so every matrix
     // must come from commit / commit_columns (which keep those digits); otherwise EON_E_ARG.
     std::vector<Opened> open(const std::vector<OpenRound>& rounds);
+    // init_srs_unsafe's g2_alpha = [alpha] G2 (params.rs:123-139), the verifier's half of the SRS:
+    // made by eon_g2_mul at the first verify and kept
+    const eon_g2_affine& g2_alpha();
 
   private:
     eon_ctx* ctx_;
     uint64_t max_degree_;
+    Fr srs_alpha_;
+    bool have_g2_alpha_ = false;
+    eon_g2_affine g2_alpha_{};
     eon_msm_bases* bases_ = nullptr;
     eon_ctx* aux_ = nullptr;
     void* aux_stream_ = nullptr;

@@ -23,7 +23,7 @@ from . import _lib
 from .collective import ALL_GATHER_FN, TorchCollective, eon_collective  # noqa: F401 (re-exported)
 from .dft import Context, default_context
 from .field import fr_to_abi, fr_unmont
-from .proof import Opened, Proof, log_quotient_degree
+from .proof import Opened, Proof, VerificationError, log_quotient_degree  # noqa: F401 (re-exported)
 
 PROVE_LIB_PATH = Path(__file__).resolve().parent / "libeonprove.so"
 
@@ -90,6 +90,10 @@ SIGNATURES = {
     "eon_prove_air_pp_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_pp), _P, _P]),
     "eon_prove_air_lk": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_lk)]),
     "eon_prove_air_lk_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, ctypes.POINTER(eon_proof_lk), _P, _P, _P]),
+    "eon_verify_air": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _P, _U32, _U32, _U32, _P, _P, _U32, _P, _P,
+                              ctypes.POINTER(_INT)]),
+    "eon_verify_air_fs": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _P, _U32, _U32, _U32, _P, _P,
+                                 ctypes.POINTER(_INT), _P, _P, _P]),
 }
 
 _plib = None
@@ -379,6 +383,115 @@ def setup_preprocessed(pcs: NativeKzgPcs, pre_trace) -> Preprocessed:
     pcs.check(pcs.lib.eon_setup_preprocessed(pcs._h, ctypes.c_void_p(t.data_ptr()), int(t.shape[0]), int(t.shape[1]),
                                              ctypes.byref(h)))
     return Preprocessed(pcs, h)
+
+
+def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: Challenger | None = None,
+                  preprocessed_vk=None, transcript: dict | None = None) -> None:
+    """verify_with_preprocessed (eon-uni-stark/src/verifier.rs:244-502) through the C++ driver
+    (eon_verify_air[_fs]).  `prog` is the air.AirProgram of the AIR (for a Poseidon2 proof of the
+    fused kernel: AirProgram(Poseidon2Air), the same constraints in the same order); `proof` has
+    prove_native's shape; `preprocessed_vk` is the verifier key, a Preprocessed or a
+    (width, degree_bits, commitment) tuple -- its commitment is the one observed and checked, never
+    the proof's copy.  With `challenger` the challenges are re-derived from the transcript and the
+    challenger ends where the prover's did; without, proof.alpha, proof.zeta and
+    proof.permutation_challenges are used.  `transcript` (a dict, optional) receives the alpha, zeta
+    and permutation_challenges the verifier used.  Returns None when the proof is valid; raises
+    VerificationError whose `.kind` names the reference's variant.  Array shapes that do not fit the
+    program (opened widths, the chunk count, the permutation width, the key's width) raise
+    InvalidProofShape before any C call."""
+    if public_values is None:
+        public_values = ()
+    from .air import _publics_limbs
+
+    def bad_shape(why):
+        return VerificationError("InvalidProofShape", why)
+
+    def mat(a, cols):
+        return np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, cols))
+
+    def pair(op, cols, what, width):
+        """[values, witnesses] of one matrix at {zeta, zeta h} as (2, width, .) arrays"""
+        if len(op.values) != 1 or len(op.values[0]) != 2 or len(op.witnesses) != 1 or len(op.witnesses[0]) != 2:
+            raise bad_shape(f"{what}: one matrix opened at two points expected")
+        v = [mat(x, 4) for x in op.values[0]]
+        w = [mat(x, 8) for x in op.witnesses[0]]
+        if any(x.shape[0] != width for x in v + w):
+            raise bad_shape(f"{what}: opened widths {[x.shape[0] for x in v + w]}, expected {width}")
+        return np.ascontiguousarray(np.stack(v)), np.ascontiguousarray(np.stack(w))
+
+    has_perm = proof.permutation_commit is not None
+    opened = list(proof.opened)
+    if len(opened) < 2 + (1 if has_perm else 0) or len(opened) > 3 + (1 if has_perm else 0):
+        raise bad_shape(f"{len(opened)} opening rounds")
+    tc = mat(proof.trace_commit[0], 8)
+    if tc.shape[0] != prog.width:
+        raise bad_shape(f"trace commitment of {tc.shape[0]} columns, the AIR has {prog.width}")
+    to, tw = pair(opened[0], 4, "trace", prog.width)
+    mc = mo = mw = None
+    if has_perm:
+        mc = mat(proof.permutation_commit[0], 8)
+        if mc.shape[0] != prog.permutation_width:
+            raise bad_shape(f"permutation commitment of {mc.shape[0]} columns, the AIR has {prog.permutation_width}")
+        mo, mw = pair(opened[1], 4, "permutation", prog.permutation_width)
+    quot = opened[2 if has_perm else 1]
+    chunks = 1 << prog.log_quotient_degree()
+    qc = np.ascontiguousarray(np.stack([mat(c, 8) for c in proof.quotient_commit]).reshape(-1, 8)) \
+        if len(proof.quotient_commit) else np.zeros((0, 8), np.uint64)
+    if qc.shape[0] != chunks or len(quot.values) != chunks or len(quot.witnesses) != chunks:
+        raise bad_shape(f"{qc.shape[0]} quotient chunk commitments, {len(quot.values)} opened, expected {chunks}")
+    if any(len(v) != 1 or mat(v[0], 4).shape[0] != 1 for v in quot.values) or \
+            any(len(w) != 1 or mat(w[0], 8).shape[0] != 1 for w in quot.witnesses):
+        raise bad_shape("each quotient chunk is one column opened at one point")
+    qo = np.ascontiguousarray(np.stack([mat(v[0], 4)[0] for v in quot.values]))
+    qw = np.ascontiguousarray(np.stack([mat(w[0], 8)[0] for w in quot.witnesses]))
+    vk_w = vk_bits = 0
+    vk_c = None
+    if preprocessed_vk is not None:
+        if isinstance(preprocessed_vk, Preprocessed):
+            vk_w, vk_bits, vk_c = preprocessed_vk.width, preprocessed_vk.degree_bits, preprocessed_vk.commitment
+        else:
+            vk_w, vk_bits, vk_c = preprocessed_vk
+        vk_w, vk_bits = int(vk_w), int(vk_bits)
+        vk_c = mat(vk_c, 8) if vk_w else np.zeros((1, 8), np.uint64)
+        if vk_w and vk_c.shape[0] != vk_w:
+            raise ValueError(f"the verifier key's commitment has {vk_c.shape[0]} columns, its width is {vk_w}")
+    po = pw = None
+    if len(opened) > (3 if has_perm else 2):  # the proof opens preprocessed columns
+        # process_preprocessed_trace (verifier.rs:184-201): the expected width is the key's, else the AIR's
+        expect = vk_w if preprocessed_vk is not None else prog.preprocessed_width
+        po, pw = pair(opened[-1], 4, "preprocessed", expect)
+    out = eon_proof(_p(tc), _p(qc), _p(to), _p(tw), _p(qo), _p(qw), int(proof.degree_bits))
+    out_pp = eon_proof_pp(out, None, _p(po) if po is not None else None, _p(pw) if pw is not None else None)
+    out_lk = eon_proof_lk(out_pp, _p(mc) if mc is not None else None, _p(mo) if mo is not None else None,
+                          _p(mw) if mw is not None else None)
+    pub = _publics_limbs(public_values)
+    npub = len(public_values)
+    pcs.ctx.set_stream(None)
+    res = _INT(-1)
+    vkp = _p(vk_c) if vk_c is not None else None
+    unm = lambda v: fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v)))  # noqa: E731
+    if challenger is None:
+        chal = [int(c) for c in (proof.permutation_challenges or ())] if has_perm else []
+        if len(chal) != (prog.num_challenges if has_perm else 0):
+            raise bad_shape(f"{len(chal)} permutation challenges, the AIR has {prog.num_challenges}")
+        ch = _publics_limbs(chal)
+        a, z = fr_to_abi(proof.alpha), fr_to_abi(proof.zeta)
+        pcs.check(pcs.lib.eon_verify_air(pcs._h, prog.handle, ctypes.byref(out_lk), _p(pub), npub, vk_w, vk_bits, vkp,
+                                         _p(ch), len(chal), ctypes.byref(a), ctypes.byref(z), ctypes.byref(res)))
+        used = {"alpha": proof.alpha, "zeta": proof.zeta, "permutation_challenges": chal}
+    else:
+        a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+        c_out = np.zeros((max(1, prog.num_challenges), 4), np.uint64)
+        pcs.check(pcs.lib.eon_verify_air_fs(pcs._h, prog.handle, ctypes.byref(out_lk), _p(pub), npub, vk_w, vk_bits,
+                                            vkp, challenger.handle, ctypes.byref(res), _p(c_out), _p(a_out),
+                                            _p(z_out)))
+        used = {"alpha": unm(a_out), "zeta": unm(z_out),
+                "permutation_challenges": [unm(c) for c in c_out[:prog.num_challenges]] if has_perm else []}
+    if transcript is not None and res.value != 1:  # a shape rejection comes before the transcript
+        transcript.update(used)
+    if res.value != 0:
+        raise VerificationError(VerificationError.KINDS[res.value], pcs.lib.eon_kzg_pcs_last_error(pcs._h).decode())
+    return None
 
 
 def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | None,

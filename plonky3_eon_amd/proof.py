@@ -33,6 +33,19 @@ class Proof:
     permutation_challenges: list | None = None
 
 
+class VerificationError(Exception):
+    """native.verify_native rejected a proof.  `kind` names the reference's VerificationError
+    variant (eon-uni-stark/src/verifier.rs:504-526): "InvalidProofShape", "InvalidOpeningArgument" or
+    "OodEvaluationMismatch"."""
+
+    KINDS = {1: "InvalidProofShape", 2: "InvalidOpeningArgument", 3: "OodEvaluationMismatch"}
+
+    def __init__(self, kind: str, detail: str = ""):
+        super().__init__(f"{kind}: {detail}" if detail else kind)
+        self.kind = kind
+        self.detail = detail
+
+
 def log_quotient_degree(max_constraint_degree: int) -> int:
     """get_log_quotient_degree (eon-uni-stark/src/symbolic_builder.rs:15-43), ZK off."""
     d = max(max_constraint_degree, 2) - 1
