@@ -246,6 +246,8 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   11: KzgMmcs -- eon_quotient_and_eval_columns_multi_dev, eon_kzg_mmcs_local_index / _open_dev /
+ *       _verify_batch and eon_mmcs_matrix, additive;
  *   10: eon_air_eval_at_point_dev, the compiled constraints at one out-of-domain point, additive;
  *   9: eon_check_constraints_dev and eon_constraint_report, EON_E_CONSTRAINT, additive;
  *   8: eon_diag_ec29_op, the curve formulas of the MSM bucket sums one per thread, additive;
@@ -347,6 +349,21 @@ int eon_quotient_and_eval_columns_dev(eon_ctx* ctx, const eon_fr* coeffs, uint64
  * coefficients serves up to four points (KzgPcs::open's opened values, kzg/src/pcs.rs:305-316). */
 int eon_eval_columns_dev(eon_ctx* ctx, const eon_fr* coeffs, uint64_t rows, uint32_t width,
                          const eon_fr* points, uint32_t npoints, eon_fr* values);
+/* quotient_and_eval (kzg/src/util.rs:100-111) for every column of the rows x width coefficient
+ * matrix (device) at npoints points (host array of canonical Fr) in one pass over the coefficients,
+ * as KzgMmcs::open_batch needs it per (matrix, local index, column) (kzg/src/mmcs.rs:223-230):
+ * values (device) receives npoints x width Fr, values[t * width + j] = f_j(points[t]); quotients
+ * (device) ONE row-major (rows-1) x (npoints*width) matrix whose column t * width + j is the
+ * synthetic-division quotient of column j by (X - points[t]) -- the quotients side by side, so that
+ * one eon_msm_g1_columns_dev over bases[0..rows-1) gives every witness.  Every output is canonical
+ * and bit-identical to eon_quotient_and_eval_columns_dev called once per point.  One load of a
+ * coefficient serves up to four points; more points run in groups of four.  width == 0 or
+ * npoints == 0: nothing is written; rows == 0: zero values; rows == 1: values only (the quotients
+ * are empty); quotients NULL: values only.  EON_E_ARG for a point that is not canonical and for a
+ * NULL pointer that would be read or written. */
+int eon_quotient_and_eval_columns_multi_dev(eon_ctx* ctx, const eon_fr* coeffs, uint64_t rows, uint32_t width,
+                                            const eon_fr* points, uint32_t npoints,
+                                            eon_fr* quotients, eon_fr* values);
 /* As eon_msm_bases_create with `bases` a DEVICE pointer (coordinates are not re-validated). */
 int eon_msm_bases_create_dev(eon_ctx* ctx, const eon_g1_affine* bases, uint64_t n, uint32_t flags,
                              eon_msm_bases** out);
@@ -691,6 +708,49 @@ int eon_multi_pairing(eon_ctx* ctx, const eon_g1_affine* p, const eon_g2_affine*
 int eon_kzg_verify_batch(eon_ctx* ctx, const eon_g1_affine* commitments, const eon_g1_affine* witnesses,
                          const eon_fr* values, const eon_fr* points, uint64_t n, const eon_g2_affine* g2_alpha,
                          int* ok);
+
+/* ---- KzgMmcs: Mmcs<Fr> over the same SRS (kzg/src/mmcs.rs) -----------------------------------
+ * A batch of matrices of mixed heights (any height >= 1, powers of two or not), every column a
+ * polynomial in COEFFICIENT form.  commit is eon_msm_g1_columns_dev per matrix (commit_matrix,
+ * mmcs.rs:155-165).  A query index opens, in matrix m, the point z = Fr::new(local_index):
+ *
+ * eon_kzg_mmcs_local_index: the index mapping of open_batch and verify_batch (mmcs.rs:213-218,
+ *   :272-277): with log2_x = next_power_of_two(x).trailing_zeros(),
+ *   local = (log2_max >= log2_h ? index >> (log2_max - log2_h) : index) % height.  Pure host
+ *   function, no context.  height == 0 returns UINT64_MAX (the reference divides by zero).
+ *
+ * eon_kzg_mmcs_open_dev: open_batch (mmcs.rs:196-236) for nidx indices at once.  `mats` (host array
+ *   of nmats descriptors; coeffs DEVICE pointers, row-major height x width), max_height = the largest
+ *   height among them.  With W = the sum of the widths, `values` (host, nidx x W Fr) and `witnesses`
+ *   (host, nidx x W points) are filled matrices in order, columns in order:
+ *   values[q * W + off_m + j] = f_j(z), witnesses[...] = commit_column(quotient_and_eval(column j,
+ *   z).0) over srs[0..height-1).  Per matrix the distinct local indices over all queries are
+ *   computed once (short matrices map many queries to one row) and copied to every query that uses
+ *   them: eon_quotient_and_eval_columns_multi_dev over the distinct points, then one column MSM over
+ *   the side-by-side quotients.  The distinct points run in groups whose quotient scratch is at most
+ *   1 GiB (a single point above that still runs; EON_MMCS_GROUP_BYTES, read at each call, sets
+ *   another cap -- the tests' way to several groups at small shapes).  height == 1: the witness is the identity and the
+ *   value c_0.  height == 0 is EON_E_SHAPE (the reference panics), height > eon_msm_bases_len(srs)
+ *   -- ensure_supported(height - 1) -- EON_E_DEGREE_TOO_LARGE.  Synchronous: returns with the host
+ *   arrays filled.
+ *
+ * eon_kzg_mmcs_verify_batch: verify_batch (mmcs.rs:242-294) for one index.  `commitments`, `values`
+ *   and `witnesses` (host) hold W entries each, laid out by `heights` / `widths` (nmats entries) as
+ *   above.  Per matrix ensure_supported(height - 1) against max_degree (EON_E_DEGREE_TOO_LARGE;
+ *   height == 0 is EON_E_SHAPE), then the (commitment, witness, value, Fr::new(local_index)) list
+ *   goes to one eon_kzg_verify_batch.  *ok = 0 is the reference's Err(ProofShapeMismatch). */
+typedef struct {
+    const eon_fr* coeffs; /* device */
+    uint64_t height;
+    uint32_t width;
+} eon_mmcs_matrix;
+uint64_t eon_kzg_mmcs_local_index(uint64_t max_height, uint64_t height, uint64_t index);
+int eon_kzg_mmcs_open_dev(eon_ctx* ctx, const eon_msm_bases* srs, const eon_mmcs_matrix* mats, uint32_t nmats,
+                          const uint64_t* indices, uint32_t nidx, eon_fr* values, eon_g1_affine* witnesses);
+int eon_kzg_mmcs_verify_batch(eon_ctx* ctx, const eon_g1_affine* commitments, const uint64_t* heights,
+                              const uint32_t* widths, uint32_t nmats, uint64_t index, const eon_fr* values,
+                              const eon_g1_affine* witnesses, uint64_t max_degree,
+                              const eon_g2_affine* g2_alpha, int* ok);
 
 #ifdef __cplusplus
 }

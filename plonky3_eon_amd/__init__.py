@@ -5,6 +5,7 @@ mirror of the reference's interfaces over that ABI:
 
 * ``dft``   -- TwoAdicSubgroupDft<Fr> (Radix2Dit / Radix2DitParallel), dft/src/traits.rs
 * ``field`` -- Fr value formatting for the ABI
+* ``mmcs``  -- KzgMmcs, Mmcs<Fr> over the KZG SRS, kzg/src/mmcs.rs
 
 There is no CPU fallback: importing an entry point loads libeonhip.so and raises if it is absent.
 """
@@ -13,6 +14,7 @@ from . import _lib  # noqa: F401
 from .dft import Context, Radix2Dit, Radix2DitParallel, BitReversedMatrix, default_context  # noqa: F401
 from ._lib import EonError  # noqa: F401
 from .proof import VerificationError  # noqa: F401  (native.verify_native's rejection)
+from .mmcs import DegreeTooLarge, KzgMmcs, ProofShapeMismatch  # noqa: F401  (kzg/src/mmcs.rs)
 
 __all__ = ["Context", "Radix2Dit", "Radix2DitParallel", "BitReversedMatrix", "default_context", "EonError",
-           "VerificationError"]
+           "VerificationError", "KzgMmcs", "DegreeTooLarge", "ProofShapeMismatch"]

@@ -24,7 +24,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 10  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 11  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -90,6 +90,10 @@ class eon_g1_affine(ctypes.Structure):
     _fields_ = [("x", ctypes.c_uint64 * 4), ("y", ctypes.c_uint64 * 4)]
 
 
+class eon_mmcs_matrix(ctypes.Structure):
+    _fields_ = [("coeffs", ctypes.c_void_p), ("height", ctypes.c_uint64), ("width", ctypes.c_uint32)]
+
+
 _P = ctypes.c_void_p
 _U32 = ctypes.c_uint32
 _U64 = ctypes.c_uint64
@@ -145,6 +149,11 @@ SIGNATURES = {
     "eon_msm_g1_columns_dev": (_INT, [_P, _P, _P, _U64, _U32, _P]),
     "eon_quotient_and_eval_columns_dev": (_INT, [_P, _P, _U64, _U32, _P, _P, _P]),
     "eon_eval_columns_dev": (_INT, [_P, _P, _U64, _U32, _P, _U32, _P]),
+    "eon_quotient_and_eval_columns_multi_dev": (_INT, [_P, _P, _U64, _U32, _P, _U32, _P, _P]),
+    "eon_kzg_mmcs_local_index": (_U64, [_U64, _U64, _U64]),
+    "eon_kzg_mmcs_open_dev": (_INT, [_P, _P, _P, _U32, _P, _U32, _P, _P]),
+    "eon_kzg_mmcs_verify_batch": (_INT, [_P, _P, _P, _P, _U32, _U64, _P, _P, _U64, _P,
+                                         ctypes.POINTER(ctypes.c_int)]),
     "eon_msm_g1_columns_prepare_dev": (_INT, [_P, _P, _P, _U64, _U32, _P, ctypes.POINTER(_P)]),
     "eon_msm_g1_columns_prepared": (_INT, [_P, _P, _U32, _P, _P]),
     "eon_msm_scalars_destroy": (None, [_P]),

@@ -260,6 +260,11 @@ Status dft_natural_dev(eon_ctx* ctx, const Fr* in, Fr* out, uint64_t height, uin
 Status fourstep_twiddle_pack(eon_ctx* ctx, const Fr* y, uint32_t log_n, uint32_t log_n1, uint64_t col0,
                              uint32_t cols, uint32_t parts, Fr* send);
 
+// quotient_and_eval of every column at npoints host points in one pass (kzg.hip; the body of
+// eon_quotient_and_eval_columns_multi_dev, caller holds ctx->mu): device c / quotients / values
+Status quotient_and_eval_multi(eon_ctx* ctx, const Fr* c, uint64_t rows, uint32_t width, const Fr* points,
+                               uint32_t npoints, Fr* quotients, Fr* values);
+
 inline Fr fr_two_adic_generator(uint32_t bits) {
     // bn254/src/field.rs:556-573: square TWO_ADIC_GENERATOR (order 2^28) 28 - bits times
     Fr w;
