@@ -441,6 +441,26 @@ int eon_p2air_quotient_values_dev(eon_ctx* ctx, const eon_p2air* air, const eon_
                                   uint32_t log_n, uint32_t log_qd, const eon_fr* alpha,
                                   eon_fr* out);
 
+/* ---- Keccak-AIR witness generation (keccak-air/src/{columns,generation}.rs) -------------------
+ * One row per round of Keccak-f[1600], 24 rows per permutation, KeccakCols order: step_flags[24],
+ * export, preimage[5][5][4], a[5][5][4], c[5][64], c_prime[5][64], a_prime[5][5][64],
+ * a_prime_prime[5][5][4], a_prime_prime_0_0_bits[64], a_prime_prime_prime_0_0_limbs[4]; the 5x5
+ * arrays y-major, a u64 as four 16-bit limbs or 64 bits, little-endian.  The constraints go through
+ * the generic AIR program below like any other EonAir. */
+/* NUM_KECCAK_COLS (columns.rs:120): 2633 */
+uint32_t eon_keccak_air_width(void);
+/* the trace height of n_hashes permutations, (24 n_hashes).next_power_of_two() (generation.rs:21);
+ * 0 for n_hashes == 0 */
+uint64_t eon_keccak_air_rows(uint64_t n_hashes);
+/* generate_trace_rows (generation.rs:17-46): `inputs` n_hashes x 25 u64 (device), input[5x + y] the
+ * lane of preimage[y][x] (the reference transmutes [u64; 25] to a state indexed [x][y]); `trace`
+ * n_rows x 2633 Fr (device), on ctx's stream.  Permutations past n_hashes take the all-zero input,
+ * the last one is cut to the rows that remain, export is 0.  n_rows != eon_keccak_air_rows(n_hashes)
+ * is EON_E_SHAPE, and so is n_hashes == 0: the reference builds a 1-row all-zero trace there that
+ * its own eval cannot read (no next row, no first step flag). */
+int eon_keccak_generate_trace_dev(eon_ctx* ctx, const uint64_t* inputs, uint64_t n_hashes, eon_fr* trace,
+                                  uint64_t n_rows);
+
 /* ---- generic AIR: quotient_values for any EonAir ---------------------------------------------
  * The constraints get_symbolic_constraints returns (eon-uni-stark/src/symbolic_builder.rs:72-126)
  * as a DAG of SymbolicExpression nodes (symbolic_expression.rs:78-145; SymbolicVariable /

@@ -6,6 +6,7 @@ mirror of the reference's interfaces over that ABI:
 * ``dft``   -- TwoAdicSubgroupDft<Fr> (Radix2Dit / Radix2DitParallel), dft/src/traits.rs
 * ``field`` -- Fr value formatting for the ABI
 * ``mmcs``  -- KzgMmcs, Mmcs<Fr> over the KZG SRS, kzg/src/mmcs.rs
+* ``keccak`` -- KeccakAir, keccak-air/src/air.rs (device trace generation, symbolic constraints)
 
 There is no CPU fallback: importing an entry point loads libeonhip.so and raises if it is absent.
 """
@@ -15,6 +16,7 @@ from .dft import Context, Radix2Dit, Radix2DitParallel, BitReversedMatrix, defau
 from ._lib import EonError  # noqa: F401
 from .proof import VerificationError  # noqa: F401  (native.verify_native's rejection)
 from .mmcs import DegreeTooLarge, KzgMmcs, ProofShapeMismatch  # noqa: F401  (kzg/src/mmcs.rs)
+from .keccak import KeccakAir  # noqa: F401  (keccak-air/src/air.rs)
 
 __all__ = ["Context", "Radix2Dit", "Radix2DitParallel", "BitReversedMatrix", "default_context", "EonError",
-           "VerificationError", "KzgMmcs", "DegreeTooLarge", "ProofShapeMismatch"]
+           "VerificationError", "KzgMmcs", "DegreeTooLarge", "ProofShapeMismatch", "KeccakAir"]

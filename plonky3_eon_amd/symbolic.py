@@ -152,6 +152,24 @@ class SymbolicExpression:
         """andn(x, x) = (1 - x) * x (field/src/field.rs:196-209)."""
         return (SymbolicExpression.constant(1) - self) * self
 
+    @staticmethod
+    def from_bool(b: bool) -> "SymbolicExpression":
+        """PrimeCharacteristicRing::from_bool (field/src/field.rs:119-125): ONE or ZERO."""
+        return SymbolicExpression.constant(1 if b else 0)
+
+    def xor(self, y):
+        """x + y - x * y.double() (field/src/field.rs:173-180): degree deg x + deg y."""
+        y = SymbolicExpression.lift(y)
+        return self + y - self * y.double()
+
+    def xor3(self, y, z):
+        """x.xor(y).xor(z) (field/src/field.rs:182-189)."""
+        return self.xor(y).xor(z)
+
+    def andn(self, y):
+        """(1 - x) * y (field/src/field.rs:191-198)."""
+        return (SymbolicExpression.constant(1) - self) * SymbolicExpression.lift(y)
+
     def __repr__(self):
         if self.op == "const":
             return f"C({self.value})"
@@ -219,6 +237,15 @@ class SymbolicVariable:
 
     def double(self):
         return self._e().double()
+
+    def xor(self, y):
+        return self._e().xor(y)
+
+    def xor3(self, y, z):
+        return self._e().xor3(y, z)
+
+    def andn(self, y):
+        return self._e().andn(y)
 
     def __repr__(self):
         if self.entry.kind in ("public", "challenge"):
