@@ -461,6 +461,29 @@ uint64_t eon_keccak_air_rows(uint64_t n_hashes);
 int eon_keccak_generate_trace_dev(eon_ctx* ctx, const uint64_t* inputs, uint64_t n_hashes, eon_fr* trace,
                                   uint64_t n_rows);
 
+/* ---- Blake3-AIR witness generation (blake3-air/src/{columns,generation}.rs) -------------------
+ * One row per BLAKE3 compression (7 rounds), Blake3Cols order: inputs[16][32], chaining_values[2][4][32],
+ * counter_low[32], counter_hi[32], block_len[32], flags[32], initial_row0[4][2], initial_row2[4][2],
+ * full_rounds[7] (each state_prime, state_middle, state_middle_prime, state_output; a state is
+ * row0[4][2], row1[4][32], row2[4][2], row3[4][32]), final_round_helpers[4][32], outputs[4][4][32]; a u32
+ * as 32 bits or two 16-bit limbs, little-endian.  The constraints go through the generic AIR program
+ * below like any other EonAir. */
+/* NUM_BLAKE3_COLS (columns.rs): 9168 */
+uint32_t eon_blake3_air_width(void);
+/* generate_trace_rows (generation.rs:16-46) with generate_trace_rows_for_perm, generate_trace_row_for_round,
+ * verifiable_half_round and save_state_to_trace (generation.rs:49-250): `inputs` n_hashes x 24 u32
+ * (device), words 0..15 the block and 16..23 the chaining value; `trace` n_rows x 9168 Fr (device), on
+ * ctx's stream.  Row k has counter = k, block_len = n_hashes, flags = 0 (generation.rs:38-43, 63-68).
+ * EON_E_SHAPE: n_hashes == 0 or not a power of two (the reference asserts it, generation.rs:21-24),
+ * n_rows != n_hashes, n_rows > 2^28. */
+int eon_blake3_generate_trace_dev(eon_ctx* ctx, const uint32_t* inputs, uint64_t n_hashes, eon_fr* trace,
+                                  uint64_t n_rows);
+/* The same with the number of workgroups that share a row given: parts = 1, 2, 4, 8 or 16 (each
+ * redoes the compression and stores one slice of the row), 0 = the library's choice, which is what
+ * eon_blake3_generate_trace_dev takes.  The trace does not depend on it; it is there to be timed. */
+int eon_diag_blake3_trace_parts(eon_ctx* ctx, const uint32_t* inputs, uint64_t n_hashes, eon_fr* trace, uint64_t n_rows,
+                                uint32_t parts);
+
 /* ---- generic AIR: quotient_values for any EonAir ---------------------------------------------
  * The constraints get_symbolic_constraints returns (eon-uni-stark/src/symbolic_builder.rs:72-126)
  * as a DAG of SymbolicExpression nodes (symbolic_expression.rs:78-145; SymbolicVariable /

@@ -7,6 +7,7 @@ mirror of the reference's interfaces over that ABI:
 * ``field`` -- Fr value formatting for the ABI
 * ``mmcs``  -- KzgMmcs, Mmcs<Fr> over the KZG SRS, kzg/src/mmcs.rs
 * ``keccak`` -- KeccakAir, keccak-air/src/air.rs (device trace generation, symbolic constraints)
+* ``blake3`` -- Blake3Air, blake3-air/src/air.rs (device trace generation, symbolic constraints)
 
 There is no CPU fallback: importing an entry point loads libeonhip.so and raises if it is absent.
 """
@@ -17,6 +18,7 @@ from ._lib import EonError  # noqa: F401
 from .proof import VerificationError  # noqa: F401  (native.verify_native's rejection)
 from .mmcs import DegreeTooLarge, KzgMmcs, ProofShapeMismatch  # noqa: F401  (kzg/src/mmcs.rs)
 from .keccak import KeccakAir  # noqa: F401  (keccak-air/src/air.rs)
+from .blake3 import Blake3Air  # noqa: F401  (blake3-air/src/air.rs)
 
 __all__ = ["Context", "Radix2Dit", "Radix2DitParallel", "BitReversedMatrix", "default_context", "EonError",
-           "VerificationError", "KzgMmcs", "DegreeTooLarge", "ProofShapeMismatch", "KeccakAir"]
+           "VerificationError", "KzgMmcs", "DegreeTooLarge", "ProofShapeMismatch", "KeccakAir", "Blake3Air"]

@@ -176,6 +176,9 @@ SIGNATURES = {
     "eon_keccak_air_width": (_U32, []),
     "eon_keccak_air_rows": (_U64, [_U64]),
     "eon_keccak_generate_trace_dev": (_INT, [_P, _P, _U64, _P, _U64]),
+    "eon_blake3_air_width": (_U32, []),
+    "eon_blake3_generate_trace_dev": (_INT, [_P, _P, _U64, _P, _U64]),
+    "eon_diag_blake3_trace_parts": (_INT, [_P, _P, _U64, _P, _U64, _U32]),
     "eon_air_program_create": (_INT, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _U32, ctypes.POINTER(_P)]),
     "eon_air_program_create_pp": (_INT, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _U32, _U32, ctypes.POINTER(_P)]),
     "eon_air_program_create_lk": (_INT, [_P, _P, _U32, _P, _U32, _P, _U32, _U32, _U32, _U32, _U32, _U32, _P, _U32, _P,

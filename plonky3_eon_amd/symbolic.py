@@ -170,6 +170,10 @@ class SymbolicExpression:
         """(1 - x) * y (field/src/field.rs:191-198)."""
         return (SymbolicExpression.constant(1) - self) * SymbolicExpression.lift(y)
 
+    def mul_2exp_u64(self, exp: int):
+        """x * 2^exp (field/src/field.rs, PrimeCharacteristicRing::mul_2exp_u64): a product by a constant."""
+        return self * SymbolicExpression.constant(1 << exp)
+
     def __repr__(self):
         if self.op == "const":
             return f"C({self.value})"
@@ -368,6 +372,53 @@ class SymbolicAirBuilder(_Builder):
 
     def assert_zero(self, x):
         self.constraints.append(SymbolicExpression.lift(x))
+
+
+def pack_bits_le(bits) -> SymbolicExpression:
+    """air/src/utils.rs:14-24: v_0 + 2 v_1 + ... + 2^n v_n as a Horner chain from the top bit,
+    acc.double() + v; ZERO for no bits."""
+    acc = None
+    for v in reversed(list(bits)):
+        v = SymbolicExpression.lift(v)
+        acc = v if acc is None else acc.double() + v
+    return SymbolicExpression.constant(0) if acc is None else acc
+
+
+def _carry_checks(builder, acc_16, acc_32, carries: int):
+    """The two checks add2 / add3 share: acc (acc + 2^32) [(acc + 2 2^32)] and the same on the low
+    limbs with 2^16, acc = acc_16 + 2^16 acc_32."""
+    two_16 = SymbolicExpression.constant(1 << 16)
+    two_32 = SymbolicExpression.constant(1 << 32)
+    acc = acc_16 + acc_32.mul_2exp_u64(16)
+    checks = []
+    for v, step in ((acc, two_32), (acc_16, two_16)):
+        prod = v * (v + step)
+        if carries == 2:
+            prod = prod * (v + SymbolicExpression.constant(2 * step.value))
+        checks.append(prod)
+    builder.assert_zeros(checks)
+
+
+def add3(builder, a, b, c, d):
+    """a = b + c + d mod 2^32 on pairs of 16-bit limbs (air/src/utils.rs:82-134): two cubics, the
+    whole difference against 0, -2^32, -2 2^32 and the low limbs' against 0, -2^16, -2 2^16."""
+    E = SymbolicExpression.lift
+    _carry_checks(builder, E(a[0]) - b[0] - c[0] - d[0], E(a[1]) - b[1] - c[1] - d[1], 2)
+
+
+def add2(builder, a, b, c):
+    """a = b + c mod 2^32 on pairs of 16-bit limbs (air/src/utils.rs:147-194): two quadratics."""
+    E = SymbolicExpression.lift
+    _carry_checks(builder, E(a[0]) - b[0] - c[0], E(a[1]) - b[1] - c[1], 1)
+
+
+def xor_32_shift(builder, a, b, c, shift: int):
+    """a = b ^ (c rotated left by shift) (air/src/utils.rs:202-230): a two limbs, b and c 32 bits;
+    range-checks c, then both limb equalities."""
+    E = SymbolicExpression.lift
+    builder.assert_bools(c)
+    sums = [pack_bits_le([E(b[i]).xor(E(c[(32 + i - shift) % 32])) for i in range(lo, lo + 16)]) for lo in (0, 16)]
+    builder.assert_zeros([E(a[0]) - sums[0], E(a[1]) - sums[1]])
 
 
 def air_width(air) -> int:
