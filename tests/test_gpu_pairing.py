@@ -13,45 +13,11 @@ and the reference's KZG tests, tests/test_pairing_oracle.py):
 import numpy as np
 import pytest
 
+from mirror_pairing import fr_limbs, g1_limbs, g2_limbs, gt_limbs
 from oracle import pairing as E
 from oracle import pyoracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-def g1_limbs(p):
-    if p is None:
-        return np.zeros(8, dtype=np.uint64)
-    return np.array(O.int_to_limbs(O.fq_to_mont(p[0])) + O.int_to_limbs(O.fq_to_mont(p[1])), dtype=np.uint64)
-
-
-def g2_limbs(q):
-    if q is None:
-        return np.zeros(16, dtype=np.uint64)
-    (x0, x1), (y0, y1) = q
-    out = []
-    for v in (x0, x1, y0, y1):
-        out += O.int_to_limbs(O.fq_to_mont(v))
-    return np.array(out, dtype=np.uint64)
-
-
-def fr_limbs(x):
-    return np.array(O.int_to_limbs(O.to_mont(x % O.P)), dtype=np.uint64)
-
-
-def gt_limbs(f):
-    """oracle Fq12 (w-basis, w^12 = 18 w^6 - 82) -> the tower layout of eon_fq12: the coefficient
-    of w^k (k = 2j + i) is a + b u with u = w^6 - 9, i.e. flat[k] = a - 9 b, flat[k + 6] = b."""
-    out = np.zeros((12, 4), dtype=np.uint64)
-    for i in range(2):
-        for j in range(3):
-            k = 2 * j + i
-            b = f[k + 6] % O.Q
-            a = (f[k] + 9 * b) % O.Q
-            m = 3 * i + j
-            out[2 * m] = O.int_to_limbs(O.fq_to_mont(a))
-            out[2 * m + 1] = O.int_to_limbs(O.fq_to_mont(b))
-    return out
 
 
 def test_g2_mul_matches_oracle(gpu_ctx):
