@@ -619,7 +619,9 @@ int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog, const 
  * column c.  The last row's contribution is computed and not stored.  A zero denominator on any
  * row (the reference panics, field/src/batch_inverse.rs:17-18) is EON_E_ARG with a message naming
  * the lookup; perm_out is then unspecified.  pre_trace must be non-NULL when a tuple reads a
- * preprocessed column and NULL when the program has no preprocessed columns (EON_E_ARG). */
+ * preprocessed column and NULL when the program has no preprocessed columns (EON_E_ARG).  The term
+ * program's register file follows eon_quotient_values_lk_dev's rule (LDS, or global for very large
+ * programs and with EON_AIR_REGS=global). */
 int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* trace,
                                const eon_fr* pre_trace, uint64_t height, const eon_fr* publics, uint32_t n_public,
                                const eon_fr* challenges, uint32_t n_challenges, eon_fr* perm_out);

@@ -27,12 +27,21 @@
 // live in VGPRs, the rest in LDS (three planes: two 16-byte, one 4-byte; conflict-free accesses)
 // sized by the program's register count, or in a global buffer for very large programs.
 //
-// The same program runs two more ways, both on the TRACE domain (local = row i, next = row (i + 1)
-// mod height): k_lookup_terms emits the lookups' denominators and multiplicities, and k_air_check
-// is check_constraints (eon-uni-stark/src/check_constraints.rs:22-101): 0 / 1 row selectors and
-// every ASSERT tested for zero mod p, reduced to the first failure and the counts.  A fourth way,
-// k_air_point, is the verifier's: one evaluation at an out-of-domain point on opened values, with
-// selectors_at_point instead of coset or 0 / 1 selectors.
+// Structure: ONE interpreter (fetch, exec1, run_program over a Window and a MemRegs file) and FOUR
+// drivers, kernels that differ only in the rows they hand it and in what an ASSERT does (the
+// Window's Sink):
+//   k_air_quotient  quotient domain, next = row (i + 2^qd) mod Q, coset selectors, ASSERTs folded;
+//   k_lookup_terms  trace domain, next = row (i + 1) mod height, no selectors, no permutation
+//                   matrix; ASSERT k emits the lookups' k-th denominator or multiplicity;
+//   k_air_check     trace domain, all three matrices, 0 / 1 selectors synthesised from the row; every
+//                   ASSERT tested for zero mod p, reduced to the first failure and the counts
+//                   (check_constraints, eon-uni-stark/src/check_constraints.rs:22-101);
+//   k_air_point     the verifier's: one evaluation on six opened rows at an out-of-domain point,
+//                   selectors_at_point, ASSERTs folded.
+// What they share is written once: make_window builds every Window, reg_file every register file;
+// on the host check_args validates what the entry points take alike, plan_regs alone decides block
+// size, register-file mode and dynamic LDS, and launch_air picks the (mode, PRE, PERM) instance
+// and launches it.
 #include <algorithm>
 #include <cstdlib>
 #include <map>
@@ -118,6 +127,13 @@ __device__ __forceinline__ F29 sub29_k(const F29& a, const F29& b, uint32_t k) {
     return r;
 }
 
+__device__ __forceinline__ F29 zero29() {
+    F29 r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = 0;
+    return r;
+}
+
 // a trace cell, constant or selector (canonical, x 2^256) as x 2^261: below 2p, or below 32p
 // unreduced when the operand is marked raw (the flag is uniform: a scalar branch)
 __device__ __forceinline__ F29 ld29(const Fr* p, bool raw) {
@@ -145,6 +161,16 @@ struct MemRegs {
         top[(uint64_t)r * stride] = x.l[8];
     }
 };
+// The file of the n_regs - AIR_VREGS registers kept in memory, as lane `slot` of `stride` sees it.
+// MODE 0: in LDS (slot = the thread, stride = the block); 1: in the global buffer `gregs` (slot =
+// the row, stride = the rows of the launch, so a wave's accesses are contiguous).
+template <int MODE>
+__device__ __forceinline__ MemRegs reg_file(uint32_t n_regs, uint4* lds, uint4* gregs, uint64_t slot,
+                                            uint64_t stride) {
+    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
+    uint4* const mem = MODE == 0 ? lds : gregs;
+    return MemRegs{mem + slot, reinterpret_cast<uint32_t*>(mem + 2ull * n_mem * stride) + slot, stride};
+}
 
 // PRE: the program reads preprocessed columns.  Without them the kernel is the one-matrix kernel,
 // instruction for instruction (the second matrix's compare and select are compiled out: measured at
@@ -152,9 +178,15 @@ struct MemRegs {
 // PERM: the program reads permutation (LogUp running-sum) columns, a third matrix through the same
 // row pair: a local / next index >= W + Wp is permutation column index - (W + Wp).  Compiled out
 // likewise when absent.
-template <bool PRE, bool PERM = false>
-struct Window {
-    static constexpr bool has_pre = PRE, has_perm = PERM, terms = false, check = false;
+// Sink: what an ASSERT does, chosen at compile time (exec1).  FoldSink: the folder's Horner chain
+// (the quotient, the out-of-domain point); EmitSink: the value is stored (the lookup terms);
+// CheckSink: it is tested for zero, and the selectors are synthesised from the row.
+struct FoldSink {
+    static constexpr bool terms = false, check = false;
+};
+template <bool PRE, bool PERM, class Sink = FoldSink>
+struct Window : Sink {
+    static constexpr bool has_pre = PRE, has_perm = PERM;
     const Fr* local;
     const Fr* next;
     const Fr* pre_local;  // the preprocessed matrix's row pair (PRE only)
@@ -164,9 +196,41 @@ struct Window {
     uint32_t width;       // main width W: a local / next index >= W is preprocessed column index - W
     uint32_t perm_base;   // W + Wp (PERM only)
     const F29* table;  // program constants, then public values: x 2^261 (< 2p), converted on the host
-    const Fr* sels;   // is_first_row | is_last_row | is_transition, q each (null if unused)
-    uint64_t row, q;
+    // is_first_row | is_last_row | is_transition, q each (null if unused).  The term and check
+    // kernels never read it (a term that reaches a selector is refused at compile time; the check
+    // synthesises its selectors in fetch) and pass a valid address, the trace
+    const Fr* sels;
+    uint64_t row, q;  // q: the rows of the domain (the quotient domain; the trace height; 1)
 };
+
+// The one way to build a window: row `row` of the three "local" matrices and row `next_row` of the
+// three "next" ones (row-major, widths width / pre_width / perm_width).  The matrix kernels take
+// both rows from the same matrix and pass it twice; k_air_point passes its six opened rows with
+// row = next_row = 0.  Field by field in this order: the PERM instances keep the window in
+// scratch, and their code follows the order of these stores.
+template <bool PRE, bool PERM, class Sink = FoldSink>
+__device__ __forceinline__ Window<PRE, PERM, Sink> make_window(const Fr* local, const Fr* next, const Fr* pre_local,
+                                                               const Fr* pre_next, const Fr* perm_local,
+                                                               const Fr* perm_next, uint32_t width, uint32_t pre_width,
+                                                               uint32_t perm_width, uint64_t row, uint64_t next_row,
+                                                               uint64_t q, const F29* table, const Fr* sels,
+                                                               const Sink& sink = Sink{}) {
+    Window<PRE, PERM, Sink> w;
+    static_cast<Sink&>(w) = sink;
+    w.local = local + row * width;
+    w.next = next + next_row * width;
+    w.pre_local = PRE ? pre_local + row * pre_width : nullptr;
+    w.pre_next = PRE ? pre_next + next_row * pre_width : nullptr;
+    w.perm_local = PERM ? perm_local + row * perm_width : nullptr;
+    w.perm_next = PERM ? perm_next + next_row * perm_width : nullptr;
+    w.width = width;
+    w.perm_base = PERM ? width + pre_width : 0;
+    w.table = table;
+    w.sels = sels;
+    w.row = row;
+    w.q = q;
+    return w;
+}
 
 // the registers held in VGPRs: register j < AIR_VREGS is hj (named values, not an array: an array
 // indexed by the register number went to scratch); the register number is uniform, so the choice
@@ -295,8 +359,7 @@ __device__ __forceinline__ void exec1(const Instr& in, RF& rf, const Win& w, con
         F29 a = x, b;
         if (opc == OP_NEG) {  // 0 - x + K p
             b = x;
-#pragma unroll
-            for (int i = 0; i < 9; i++) a.l[i] = 0;
+            a = zero29();
         } else {
             b = fetch(in.b, rf, prev, hot, w);
         }
@@ -361,32 +424,14 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= q) return;
     const uint64_t next_row = (row + next_step) & (q - 1);
-    Window<PRE, PERM> w{lde + row * width,
-                        lde + next_row * width,
-                        PRE ? pre_lde + row * pre_width : nullptr,
-                        PRE ? pre_lde + next_row * pre_width : nullptr,
-                        PERM ? perm_lde + row * perm_width : nullptr,
-                        PERM ? perm_lde + next_row * perm_width : nullptr,
-                        width,
-                        PERM ? width + pre_width : 0,
-                        table,
-                  sels,
-                  row,
-                  q};
+    const auto w = make_window<PRE, PERM>(lde, lde, pre_lde, pre_lde, perm_lde, perm_lde, width, pre_width, perm_width,
+                                          row, next_row, q, table, sels);
+    // written out here and in run_program, not zero29(): with the helper the six instances of this
+    // kernel come out scheduled and allocated differently (6 to 12 instructions of 6500 to 6800)
     F29 acc;
 #pragma unroll
     for (int i = 0; i < 9; i++) acc.l[i] = 0;
-    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;  // registers in memory
-    MemRegs rf;
-    if (MODE == 0) {
-        rf.base = lds_regs + threadIdx.x;
-        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x) + threadIdx.x;
-        rf.stride = blockDim.x;
-    } else {
-        rf.base = gregs + row;
-        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem * q) + row;
-        rf.stride = q;
-    }
+    MemRegs rf = reg_file<MODE>(n_regs, lds_regs, gregs, MODE == 0 ? threadIdx.x : row, MODE == 0 ? blockDim.x : q);
     run_program(code, n_blocks, rf, w, uniform29(shl5_to261<FrP>(alpha)), acc);
     // acc (x 2^261, < (2 + B_RAW) p, limbs < 2^30) times inv_vanishing in the ABI form: x 2^261 y 2^256 2^-261
     // = x y 2^256 (prover.rs:699)
@@ -399,17 +444,8 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
 // selectors, no permutation columns.  Its k-th root is emitted (not folded) as register k of a
 // MemRegs file in global memory, in the interpreter's own form (x 2^261, < 32p): planes of `height`
 // rows, so a wave's stores are contiguous.  lookup.hip brings them to canonical form.
-template <bool PRE>
-struct TermWindow {
-    static constexpr bool has_pre = PRE, has_perm = false, terms = true, check = false;
-    const Fr* local;
-    const Fr* next;
-    const Fr* pre_local;
-    const Fr* pre_next;
-    uint32_t width;
-    const F29* table;  // program constants, public values, challenges
-    const Fr* sels;    // never read (a term that reaches a selector is refused at compile time); a valid address
-    uint64_t row, q;
+struct EmitSink {
+    static constexpr bool terms = true, check = false;
     MemRegs out;  // this row's view of the emitted values
     __device__ __forceinline__ void emit(uint32_t k, const F29& x) const {
         MemRegs o = out;
@@ -430,31 +466,14 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_lookup_terms(const CodeBlock* __r
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= height) return;
     const uint64_t next_row = row + 1 == height ? 0 : row + 1;
-    TermWindow<PRE> w{trace + row * width,
-                      trace + next_row * width,
-                      PRE ? pre + row * pre_width : nullptr,
-                      PRE ? pre + next_row * pre_width : nullptr,
-                      width,
-                      table,
-                      trace,
-                      row,
-                      height,
-                      MemRegs{planes + row, reinterpret_cast<uint32_t*>(planes + 2ull * n_out * height) + row, height}};
-    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
-    MemRegs rf;
-    if (MODE == 0) {
-        rf.base = lds_regs + threadIdx.x;
-        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x) + threadIdx.x;
-        rf.stride = blockDim.x;
-    } else {
-        rf.base = gregs + row;
-        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem * height) + row;
-        rf.stride = height;
-    }
-    F29 acc, zero;
-#pragma unroll
-    for (int i = 0; i < 9; i++) acc.l[i] = zero.l[i] = 0;
-    run_program(code, n_blocks, rf, w, zero, acc);
+    const EmitSink sink{
+        MemRegs{planes + row, reinterpret_cast<uint32_t*>(planes + 2ull * n_out * height) + row, height}};
+    const auto w = make_window<PRE, false>(trace, trace, pre, pre, nullptr, nullptr, width, pre_width, 0, row, next_row,
+                                           height, table, trace, sink);
+    MemRegs rf =
+        reg_file<MODE>(n_regs, lds_regs, gregs, MODE == 0 ? threadIdx.x : row, MODE == 0 ? blockDim.x : height);
+    F29 acc = zero29();
+    run_program(code, n_blocks, rf, w, zero29(), acc);
 }
 
 // ---- check_constraints (eon-uni-stark/src/check_constraints.rs:22-101) ------------------------------
@@ -479,21 +498,9 @@ struct CheckState {
     uint32_t first = NO_FAIL;  // this lane's first failing constraint
     uint64_t total = 0;        // the wave's failures so far (uniform)
 };
-template <bool PRE, bool PERM>
-struct CheckWindow {
-    static constexpr bool has_pre = PRE, has_perm = PERM, terms = false, check = true;
-    const Fr* local;
-    const Fr* next;
-    const Fr* pre_local;
-    const Fr* pre_next;
-    const Fr* perm_local;
-    const Fr* perm_next;
-    uint32_t width;
-    uint32_t perm_base;
-    const F29* table;  // program constants, public values, challenges
-    const Fr* sels;    // never read (the selectors are synthesised in fetch); a valid address
-    uint64_t row, q;   // q = the trace height
-    uint32_t target;   // NO_FAIL: count failures; else store that ASSERT's value
+struct CheckSink {
+    static constexpr bool terms = false, check = true;
+    uint32_t target;  // NO_FAIL: count failures; else store that ASSERT's value
     uint32_t* per_constraint;
     Fr* value_out;
     mutable CheckState st;
@@ -538,37 +545,13 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_check(const CodeBlock* __rest
     if (t >= n_rows) return;
     const uint64_t row = row0 + t;
     const uint64_t next_row = row + 1 == height ? 0 : row + 1;
-    CheckWindow<PRE, PERM> w{trace + row * width,
-                             trace + next_row * width,
-                             PRE ? pre + row * pre_width : nullptr,
-                             PRE ? pre + next_row * pre_width : nullptr,
-                             PERM ? perm + row * perm_width : nullptr,
-                             PERM ? perm + next_row * perm_width : nullptr,
-                             width,
-                             PERM ? width + pre_width : 0,
-                             table,
-                             trace,
-                             row,
-                             height,
-                             target,
-                             per_constraint,
-                             value_out,
-                             CheckState{}};
-    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
-    MemRegs rf;
-    if (MODE == 0) {
-        rf.base = lds_regs + threadIdx.x;
-        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x) + threadIdx.x;
-        rf.stride = blockDim.x;
-    } else {
-        rf.base = gregs + row;
-        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem * height) + row;
-        rf.stride = height;
-    }
-    F29 acc, zero;
-#pragma unroll
-    for (int i = 0; i < 9; i++) acc.l[i] = zero.l[i] = 0;
-    run_program(code, n_blocks, rf, w, zero, acc);
+    const auto w = make_window<PRE, PERM>(trace, trace, pre, pre, perm, perm, width, pre_width, perm_width, row,
+                                          next_row, height, table, trace,
+                                          CheckSink{target, per_constraint, value_out, {}});
+    MemRegs rf =
+        reg_file<MODE>(n_regs, lds_regs, gregs, MODE == 0 ? threadIdx.x : row, MODE == 0 ? blockDim.x : height);
+    F29 acc = zero29();
+    run_program(code, n_blocks, rf, w, zero29(), acc);
     if (target != NO_FAIL) return;
     const uint64_t any = __ballot(w.st.first != NO_FAIL);
     if (any != 0) {  // uniform
@@ -601,32 +584,11 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_point(const CodeBlock* __rest
                                                      uint4* __restrict__ gregs) {
     extern __shared__ uint4 lds_regs[];
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    Window<PRE, PERM> w{local,
-                        next,
-                        PRE ? pre_local : nullptr,
-                        PRE ? pre_next : nullptr,
-                        PERM ? perm_local : nullptr,
-                        PERM ? perm_next : nullptr,
-                        width,
-                        PERM ? width + pre_width : 0,
-                        table,
-                        sels,
-                        0,
-                        1};
-    F29 acc;
-#pragma unroll
-    for (int i = 0; i < 9; i++) acc.l[i] = 0;
-    const uint32_t n_mem = n_regs > AIR_VREGS ? n_regs - AIR_VREGS : 0;
-    MemRegs rf;
-    if (MODE == 0) {
-        rf.base = lds_regs;
-        rf.top = reinterpret_cast<uint32_t*>(lds_regs + 2ull * n_mem * blockDim.x);
-        rf.stride = blockDim.x;
-    } else {  // one row: the planes are contiguous
-        rf.base = gregs;
-        rf.top = reinterpret_cast<uint32_t*>(gregs + 2ull * n_mem);
-        rf.stride = 1;
-    }
+    const auto w = make_window<PRE, PERM>(local, next, pre_local, pre_next, perm_local, perm_next, width, pre_width, 0,
+                                          0, 0, 1, table, sels);
+    // thread 0 of the block; in the global buffer one row, so the planes are contiguous
+    MemRegs rf = reg_file<MODE>(n_regs, lds_regs, gregs, 0, MODE == 0 ? blockDim.x : 1);
+    F29 acc = zero29();
     run_program(code, n_blocks, rf, w, uniform29(shl5_to261<FrP>(alpha)), acc);
     // acc: x 2^261, < (2 + B_RAW) p, limbs < 2^30.  Times 2^256 (a plain integer < p) it is
     // x 2^256, the ABI form; times inv_vanishing in the ABI form x y 2^256 (as k_air_quotient)
@@ -666,10 +628,56 @@ int finish(eon_ctx* ctx, const Status& s) {
     return s.code;
 }
 
-// The register file of a k_air_quotient / k_air_check launch over `rows` rows: LDS (the block
-// shrinks with the register count), or the program's global buffer for very large programs and
-// with EON_AIR_REGS=global (for tests; read once per process).  MemRegs: 36 bytes per register in
-// memory.
+// the frame of an entry point: the context's lock and device around `body`, its Status kept for
+// eon_ctx_last_error
+template <class Body>
+int with_ctx(eon_ctx* ctx, Body body) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    return finish(ctx, body());
+}
+
+// A matrix argument of an entry point, given exactly when the program has such columns.  `name`:
+// as the entry's header spells it, for the message (null: the entry has no such argument); any /
+// all: of its pointers, given; `hint` ends the message of a missing one.
+struct MatArg {
+    const char* name;
+    bool any, all;
+    const char* hint;
+    static MatArg none() { return {nullptr, false, false, ""}; }
+    static MatArg one(const char* name, const void* p, const char* hint = "") { return {name, !!p, !!p, hint}; }
+    static MatArg pair(const char* name, const void* a, const void* b) { return {name, a || b, a && b, ""}; }
+    Status check(bool has, const char* kind) const {
+        if (!name || (has ? all : !any)) return Status::ok();
+        return Status::err(EON_E_ARG, std::string("the program ") + (has ? "reads " : "has no ") + kind +
+                                          " columns: " + name + (has ? " must not be null" : " must be null") +
+                                          (has ? hint : ""));
+    }
+};
+
+// What the entry points that run a program check alike, in this order: `missing` (a required
+// pointer of the entry's own is null), the context, the permutation matrix, the challenge count,
+// the preprocessed matrix, the public value count, the trace height (when the entry takes one).
+Status check_args(const eon_ctx* ctx, const eon_air_program* prog, bool missing, const MatArg& perm,
+                  const MatArg& pre, const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
+                  uint32_t n_challenges, const uint64_t* height = nullptr) {
+    if (missing || (n_public && !publics) || (n_challenges && !challenges))
+        return Status::err(EON_E_ARG, "null argument");
+    if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+    EON_TRY(perm.check(prog->perm_width > 0, "permutation"));
+    if (n_challenges != prog->n_challenges)
+        return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
+    EON_TRY(pre.check(prog->pre_width > 0, "preprocessed"));
+    if (n_public != prog->n_public) return Status::err(EON_E_SHAPE, "public value count differs from the program's");
+    if (height && (*height == 0 || (*height & (*height - 1)) || *height > (1ull << 28)))
+        return Status::err(EON_E_SHAPE, "trace height must be a power of two <= 2^28");
+    return Status::ok();
+}
+
+// The register file of a launch over `rows` rows, for all four kernels: LDS (the block shrinks
+// with the register count), or the program's global buffer for very large programs and with
+// EON_AIR_REGS=global (for tests; read once per process).  MemRegs: 36 bytes per register in
+// memory.  The only place that decides the block size, the mode and the dynamic LDS.
 struct RegFile {
     uint32_t block = AIR_BLOCK;
     int mode = 0;  // 0: LDS, 1: global
@@ -688,6 +696,54 @@ Status plan_regs(eon_air_program* prog, uint64_t rows, RegFile* out) {
     if (r.mode == 1) EON_HIP(prog->d_regs.ensure(std::max<uint64_t>(1, rows * per_thread)));
     r.shmem = r.mode == 0 ? (size_t)r.block * per_thread : 0;
     *out = r;
+    return Status::ok();
+}
+
+uint32_t code_blocks(size_t n_instr) { return (uint32_t)((n_instr + CODE_BLOCK - 1) / CODE_BLOCK); }
+
+// algorithmic 256-bit products of one run of the program: its multiplications and, where ASSERTs
+// are folded, one acc * alpha each (additions, subtractions and negations are not products)
+uint64_t products(const std::vector<Instr>& code, bool count_asserts) {
+    uint64_t n = 0;
+    for (const Instr& in : code) {
+        const uint32_t opc = in.op & OP_MASK;
+        n += (opc == OP_MUL || opc == OP_SQR || (count_asserts && opc == OP_ASSERT)) ? 1 : 0;
+    }
+    return n;
+}
+
+// the profiler's record of a launch (label null: not recorded)
+struct Profile {
+    const char* label;
+    uint64_t bytes, mulmods;
+};
+
+// Launches one of the four kernels over `rows` rows: the first `n_blocks` code blocks of `run`
+// with the register file `regs` planned for it.  `pick(mode, pre, perm)` names the kernel
+// template's instance for three std::integral_constant; every instance of a template has the same
+// function type, and every kernel takes (code, n_blocks, n_regs, args..., gregs).
+template <class Pick, class... Args>
+Status launch_air(eon_ctx* ctx, const eon_air_program* run, const RegFile& regs, uint64_t rows, uint32_t n_blocks,
+                  const Profile& prof, bool has_pre, bool has_perm, Pick pick, Args... args) {
+    constexpr std::integral_constant<int, 0> LDS{};
+    constexpr std::integral_constant<int, 1> GLOBAL{};
+    constexpr std::true_type T{};
+    constexpr std::false_type F{};
+    // a program with permutation columns runs the PRE instance whatever its preprocessed width
+    const auto kern = regs.mode == 0 ? (has_perm ? pick(LDS, T, T) : has_pre ? pick(LDS, T, F) : pick(LDS, F, F))
+                                     : (has_perm  ? pick(GLOBAL, T, T)
+                                        : has_pre ? pick(GLOBAL, T, F)
+                                                  : pick(GLOBAL, F, F));
+    if (regs.mode == 0)  // per launch: the attribute is per device, and this context's device may
+                         // differ from the one another context set it on
+        EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (prof.label) ctx->prof.begin(prof.label, prof.bytes, ctx->stream, prof.mulmods);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + regs.block - 1) / regs.block)), dim3(regs.block), regs.shmem,
+                       ctx->stream, run->d_code.as<CodeBlock>(), n_blocks, run->n_regs, args...,
+                       regs.mode == 1 ? run->d_regs.as<uint4>() : nullptr);
+    if (prof.label) ctx->prof.end(ctx->stream);
+    EON_HIP(hipGetLastError());
     return Status::ok();
 }
 
@@ -1073,9 +1129,7 @@ int eon_air_program_create_lk(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t 
                               uint32_t n_challenges, const eon_lookup_desc* lookups, uint32_t n_lookups,
                               const eon_lookup_term* terms, eon_air_program** out) {
     if (!ctx) return EON_E_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
-    Status s = [&]() -> Status {
+    return with_ctx(ctx, [&]() -> Status {
         if (!out || (n_nodes && !nodes) || (n_consts && !consts) || (n_constraints && !constraints) ||
             (n_lookups && !lookups))
             return Status::err(EON_E_ARG, "null argument");
@@ -1160,8 +1214,7 @@ int eon_air_program_create_lk(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t 
         }
         *out = p.release();
         return Status::ok();
-    }();
-    return finish(ctx, s);
+    });
 }
 
 int eon_air_program_create_pp(eon_ctx* ctx, const eon_sym_node* nodes, uint32_t n_nodes, const eon_fr* consts,
@@ -1219,25 +1272,10 @@ int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
                                uint32_t n_challenges, eon_fr* out) {
     if (!ctx || !prog_c) return EON_E_ARG;
     auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
-    Status s = [&]() -> Status {
-        if (!lde || !alpha || !out || (n_public && !publics) || (n_challenges && !challenges))
-            return Status::err(EON_E_ARG, "null argument");
-        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
-        if ((perm_lde != nullptr) != (prog->perm_width > 0))
-            return Status::err(EON_E_ARG, prog->perm_width > 0
-                                              ? "the program reads permutation columns: perm_lde must not be null "
-                                                "(eon_quotient_values_lk_dev)"
-                                              : "the program has no permutation columns: perm_lde must be null");
-        if (n_challenges != prog->n_challenges)
-            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
-        if ((pre_lde != nullptr) != (prog->pre_width > 0))
-            return Status::err(EON_E_ARG, prog->pre_width > 0
-                                              ? "the program reads preprocessed columns: pre_lde must not be null"
-                                              : "the program has no preprocessed columns: pre_lde must be null");
-        if (n_public != prog->n_public)
-            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
+    return with_ctx(ctx, [&]() -> Status {
+        EON_TRY(check_args(ctx, prog, !lde || !alpha || !out,
+                           MatArg::one("perm_lde", perm_lde, " (eon_quotient_values_lk_dev)"),
+                           MatArg::one("pre_lde", pre_lde), publics, n_public, challenges, n_challenges));
         const uint32_t log_q = log_n + log_qd;
         EON_TRY(check_domains(log_n, log_q));
         const Fr al = fr_from_abi(alpha);
@@ -1260,50 +1298,17 @@ int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
         const uint32_t nr_mask = prog->uses_sels ? (uint32_t)(q - 1) : (1u << log_qd) - 1;
         RegFile regs;
         EON_TRY(plan_regs(prog, q, &regs));
-        const uint32_t block = regs.block;
-        const int mode = regs.mode;
-        const size_t shmem = regs.shmem;
-        const unsigned grid = (unsigned)((q + block - 1) / block);
-        // algorithmic 256-bit products per row: the program's multiplications, one acc * alpha per
-        // constraint (ASSERT) and the final inv_vanishing product (additions, subtractions and
-        // negations are not products)
-        uint64_t products = 1;
-        for (const Instr& in : prog->code) {
-            const uint32_t opc = in.op & OP_MASK;
-            products += (opc == OP_MUL || opc == OP_SQR || opc == OP_ASSERT) ? 1 : 0;
-        }
-        ctx->prof.begin("k_air_quotient",
-                        q * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32 + q * 32, ctx->stream,
-                        q * products);
-        const CodeBlock* code = prog->d_code.as<CodeBlock>();
-        const uint32_t n_blocks = (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK);
-        const Fr* lde_f = reinterpret_cast<const Fr*>(lde);
-        const Fr* sel = prog->uses_sels ? prog->d_sels.as<Fr>() : nullptr;
-        Fr* out_f = reinterpret_cast<Fr*>(out);
-        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
-                                  const Fr*, uint32_t, uint64_t, uint64_t, const F29*, const Fr*, const Fr*, uint32_t,
-                                  Fr, Fr*, uint4*);
-        const bool has_pre = prog->pre_width > 0, has_perm = prog->perm_width > 0;
-        const KernelFn kern = mode == 0 ? (has_perm  ? k_air_quotient<0, true, true>
-                                           : has_pre ? k_air_quotient<0, true, false>
-                                                     : k_air_quotient<0, false, false>)
-                                        : (has_perm  ? k_air_quotient<1, true, true>
-                                           : has_pre ? k_air_quotient<1, true, false>
-                                                     : k_air_quotient<1, false, false>);
-        if (mode == 0)  // per launch: the attribute is per device, and this context's device may
-                        // differ from the one another context set it on
-            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, ctx->stream, code, n_blocks, prog->n_regs, lde_f,
-                           prog->width, reinterpret_cast<const Fr*>(pre_lde), prog->pre_width,
-                           reinterpret_cast<const Fr*>(perm_lde), prog->perm_width, q, 1ull << log_qd,
-                           prog->d_table.as<F29>(), sel, inv_van, nr_mask, al, out_f,
-                           mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
-        ctx->prof.end(ctx->stream);
-        EON_HIP(hipGetLastError());
-        return Status::ok();
-    }();
-    return finish(ctx, s);
+        // products per row: the program's, one per fold, the final inv_vanishing product
+        const Profile prof{"k_air_quotient",
+                           q * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32 + q * 32,
+                           q * (products(prog->code, true) + 1)};
+        return launch_air(
+            ctx, prog, regs, q, code_blocks(prog->code.size()), prof, prog->pre_width > 0, prog->perm_width > 0,
+            [](auto m, auto pre, auto perm) { return k_air_quotient<m(), pre(), perm()>; },
+            reinterpret_cast<const Fr*>(lde), prog->width, reinterpret_cast<const Fr*>(pre_lde), prog->pre_width,
+            reinterpret_cast<const Fr*>(perm_lde), prog->perm_width, q, 1ull << log_qd, prog->d_table.as<F29>(),
+            prog->uses_sels ? prog->d_sels.as<Fr>() : nullptr, inv_van, nr_mask, al, reinterpret_cast<Fr*>(out));
+    });
 }
 
 int eon_quotient_values_pp_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* lde, const eon_fr* pre_lde,
@@ -1336,24 +1341,16 @@ int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
                                const eon_fr* challenges, uint32_t n_challenges, eon_fr* perm_out) {
     if (!ctx || !prog_c) return EON_E_ARG;
     auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
-    Status s = [&]() -> Status {
-        if (!trace || !perm_out || (n_public && !publics) || (n_challenges && !challenges))
-            return Status::err(EON_E_ARG, "null argument");
-        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
+    return with_ctx(ctx, [&]() -> Status {
+        // no permutation matrix here, and pre_trace follows the terms, not the program (below)
+        EON_TRY(check_args(ctx, prog, !trace || !perm_out, MatArg::none(), MatArg::none(), publics, n_public,
+                           challenges, n_challenges, &height));
         if (!prog->terms)
             return Status::err(EON_E_ARG, "the program carries no lookup description (eon_air_program_create_lk)");
         if (prog->terms_read_pre != (pre_trace != nullptr) && (prog->terms_read_pre || prog->pre_width == 0))
             return Status::err(EON_E_ARG, prog->terms_read_pre
                                               ? "a lookup term reads a preprocessed column: pre_trace must not be null"
                                               : "the program has no preprocessed columns: pre_trace must be null");
-        if (n_public != prog->n_public)
-            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
-        if (n_challenges != prog->n_challenges)
-            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
-        if (height == 0 || (height & (height - 1)) || height > (1ull << 28))
-            return Status::err(EON_E_SHAPE, "trace height must be a power of two <= 2^28");
         eon_air_program* tp = prog->terms.get();
         EON_TRY(stage_table(ctx, tp, publics, n_public, challenges, n_challenges));
         const uint32_t n_lookups = (uint32_t)prog->aux.size(), n_terms = prog->term_off.back();
@@ -1362,31 +1359,15 @@ int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
         const uint64_t emitted = 2ull * n_terms * height * 48;
         EON_HIP(ctx_ensure(ctx, prog->d_terms, std::max<uint64_t>(1, emitted + (uint64_t)n_terms * height * sizeof(Fr))));
         EON_HIP(hipMemsetAsync(prog->d_flag.p, 0xff, sizeof(uint32_t), ctx->stream));
-        const uint64_t per_thread = (uint64_t)(tp->n_regs > AIR_VREGS ? tp->n_regs - AIR_VREGS : 0) * 36;
-        uint32_t block = AIR_BLOCK;
-        while (block > 64 && block * per_thread > 64 * 1024) block /= 2;
-        const int mode = block * per_thread <= 160 * 1024 ? 0 : 1;
-        if (mode != 0) block = AIR_BLOCK;
-        if (mode == 1) EON_HIP(tp->d_regs.ensure(std::max<uint64_t>(1, height * per_thread)));
-        const unsigned grid = (unsigned)((height + block - 1) / block);
-        const size_t shmem = mode == 0 ? (size_t)block * per_thread : 0;
-        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
-                                  uint64_t, const F29*, uint32_t, uint4*, uint4*);
-        const bool has_pre = pre_trace != nullptr && prog->pre_width > 0;
-        const KernelFn kern = mode == 0 ? (has_pre ? k_lookup_terms<0, true> : k_lookup_terms<0, false>)
-                                        : (has_pre ? k_lookup_terms<1, true> : k_lookup_terms<1, false>);
-        if (mode == 0)
-            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        ctx->prof.begin("k_lookup_terms", height * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32,
-                        ctx->stream);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(block), shmem, ctx->stream, tp->d_code.as<CodeBlock>(),
-                           (uint32_t)((tp->code.size() + CODE_BLOCK - 1) / CODE_BLOCK), tp->n_regs,
-                           reinterpret_cast<const Fr*>(trace), prog->width, reinterpret_cast<const Fr*>(pre_trace),
-                           prog->pre_width, height, tp->d_table.as<F29>(), 2 * n_terms, prog->d_terms.as<uint4>(),
-                           mode == 1 ? tp->d_regs.as<uint4>() : nullptr);
-        ctx->prof.end(ctx->stream);
-        EON_HIP(hipGetLastError());
+        RegFile regs;  // of the term program, over the trace's rows
+        EON_TRY(plan_regs(tp, height, &regs));
+        const Profile prof{"k_lookup_terms",
+                           height * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32, 0};
+        EON_TRY(launch_air(
+            ctx, tp, regs, height, code_blocks(tp->code.size()), prof, pre_trace != nullptr && prog->pre_width > 0,
+            false, [](auto m, auto pre, auto) { return k_lookup_terms<m(), pre()>; },
+            reinterpret_cast<const Fr*>(trace), prog->width, reinterpret_cast<const Fr*>(pre_trace), prog->pre_width,
+            height, tp->d_table.as<F29>(), 2 * n_terms, prog->d_terms.as<uint4>()));
         EON_TRY(lookup_contributions(ctx, prog->d_terms.as<uint4>(),
                                      reinterpret_cast<Fr*>(prog->d_terms.as<char>() + emitted), height, prog->d_desc.as<uint32_t>(), n_lookups,
                                      n_terms, reinterpret_cast<Fr*>(perm_out), prog->perm_width,
@@ -1401,8 +1382,7 @@ int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog_c, cons
                                               "): a denominator alpha - fold(elements, beta) is zero on some row; "
                                               "the permutation trace is not valid");
         return Status::ok();
-    }();
-    return finish(ctx, s);
+    });
 }
 
 int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* trace,
@@ -1411,26 +1391,9 @@ int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog_c, const
                               uint32_t n_challenges, uint32_t* per_constraint, eon_constraint_report* out) {
     if (!ctx || !prog_c) return EON_E_ARG;
     auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
-    Status s = [&]() -> Status {
-        if (!trace || !out || (n_public && !publics) || (n_challenges && !challenges))
-            return Status::err(EON_E_ARG, "null argument");
-        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
-        if ((perm_trace != nullptr) != (prog->perm_width > 0))
-            return Status::err(EON_E_ARG, prog->perm_width > 0
-                                              ? "the program reads permutation columns: perm_trace must not be null"
-                                              : "the program has no permutation columns: perm_trace must be null");
-        if (n_challenges != prog->n_challenges)
-            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
-        if ((pre_trace != nullptr) != (prog->pre_width > 0))
-            return Status::err(EON_E_ARG, prog->pre_width > 0
-                                              ? "the program reads preprocessed columns: pre_trace must not be null"
-                                              : "the program has no preprocessed columns: pre_trace must be null");
-        if (n_public != prog->n_public)
-            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
-        if (height == 0 || (height & (height - 1)) || height > (1ull << 28))
-            return Status::err(EON_E_SHAPE, "trace height must be a power of two <= 2^28");
+    return with_ctx(ctx, [&]() -> Status {
+        EON_TRY(check_args(ctx, prog, !trace || !out, MatArg::one("perm_trace", perm_trace),
+                           MatArg::one("pre_trace", pre_trace), publics, n_public, challenges, n_challenges, &height));
         EON_TRY(stage_table(ctx, prog, publics, n_public, challenges, n_challenges));
         *out = eon_constraint_report{};
         const uint32_t nc = prog->n_constraints;
@@ -1442,47 +1405,23 @@ int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog_c, const
         char* res = prog->d_check.as<char>();
         EON_HIP(hipMemsetAsync(res, 0, HEAD + (size_t)nc * sizeof(uint32_t), ctx->stream));
         EON_HIP(hipMemsetAsync(res, 0xff, 8, ctx->stream));
-        RegFile regs;  // the quotient's rule
+        RegFile regs;
         EON_TRY(plan_regs(prog, height, &regs));
-        const uint32_t block = regs.block;
-        const int mode = regs.mode;
-        const size_t shmem = regs.shmem;
-        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, uint32_t, const Fr*, uint32_t,
-                                  const Fr*, uint32_t, uint64_t, const F29*, uint64_t, uint64_t, uint32_t, uint32_t,
-                                  uint32_t*, unsigned long long*, Fr*, uint4*);
-        const bool has_pre = prog->pre_width > 0, has_perm = prog->perm_width > 0;
-        const KernelFn kern = mode == 0 ? (has_perm  ? k_air_check<0, true, true>
-                                           : has_pre ? k_air_check<0, true, false>
-                                                     : k_air_check<0, false, false>)
-                                        : (has_perm  ? k_air_check<1, true, true>
-                                           : has_pre ? k_air_check<1, true, false>
-                                                     : k_air_check<1, false, false>);
-        if (mode == 0)
-            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        const CodeBlock* code = prog->d_code.as<CodeBlock>();
-        const uint32_t n_blocks = (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK);
         auto* summary = reinterpret_cast<unsigned long long*>(res);
         Fr* value = reinterpret_cast<Fr*>(res + 16);
         uint32_t* counts = reinterpret_cast<uint32_t*>(res + HEAD);
-        auto launch = [&](uint64_t row0, uint64_t n_rows, uint32_t target, uint32_t run_blocks) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)((n_rows + block - 1) / block)), dim3(block), shmem, ctx->stream,
-                               code, run_blocks, prog->n_regs, reinterpret_cast<const Fr*>(trace), prog->width,
-                               reinterpret_cast<const Fr*>(pre_trace), prog->pre_width,
-                               reinterpret_cast<const Fr*>(perm_trace), prog->perm_width, height,
-                               prog->d_table.as<F29>(), row0, n_rows, target, nc, counts, summary, value,
-                               mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
+        auto launch = [&](uint64_t row0, uint64_t n_rows, uint32_t target, uint32_t run_blocks, const Profile& prof) {
+            return launch_air(
+                ctx, prog, regs, n_rows, run_blocks, prof, prog->pre_width > 0, prog->perm_width > 0,
+                [](auto m, auto pre, auto perm) { return k_air_check<m(), pre(), perm()>; },
+                reinterpret_cast<const Fr*>(trace), prog->width, reinterpret_cast<const Fr*>(pre_trace),
+                prog->pre_width, reinterpret_cast<const Fr*>(perm_trace), prog->perm_width, height,
+                prog->d_table.as<F29>(), row0, n_rows, target, nc, counts, summary, value);
         };
-        uint64_t products = 0;  // algorithmic 256-bit products per row: no folds, no inv_vanishing
-        for (const Instr& in : prog->code) {
-            const uint32_t opc = in.op & OP_MASK;
-            products += (opc == OP_MUL || opc == OP_SQR) ? 1 : 0;
-        }
-        ctx->prof.begin("k_air_check", height * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32,
-                        ctx->stream, height * products);
-        launch(0, height, NO_FAIL, n_blocks);
-        ctx->prof.end(ctx->stream);
-        EON_HIP(hipGetLastError());
+        // products per row: no folds, no inv_vanishing
+        EON_TRY(launch(0, height, NO_FAIL, code_blocks(prog->code.size()),
+                       Profile{"k_air_check", height * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32,
+                               height * products(prog->code, false)}));
         std::vector<unsigned long long> head(2);
         std::vector<uint32_t> host_counts(nc);
         EON_HIP(hipMemcpyAsync(head.data(), summary, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -1500,14 +1439,12 @@ int eon_check_constraints_dev(eon_ctx* ctx, const eon_air_program* prog_c, const
         uint32_t at = 0;
         for (uint32_t seen = 0; at < prog->code.size(); at++)
             if ((prog->code[at].op & OP_MASK) == OP_ASSERT && seen++ == out->constraint) break;
-        launch(out->row, 1, out->constraint, at / CODE_BLOCK + 1);
-        EON_HIP(hipGetLastError());
+        EON_TRY(launch(out->row, 1, out->constraint, at / CODE_BLOCK + 1, Profile{nullptr, 0, 0}));
         static_assert(sizeof(Fr) == sizeof(eon_fr), "Fr is the ABI's 32 little-endian bytes");
         EON_HIP(hipMemcpyAsync(&out->value, value, sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
-    }();
-    return finish(ctx, s);
+    });
 }
 
 int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint32_t log_n, const eon_fr* zeta,
@@ -1517,29 +1454,11 @@ int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint3
                               uint32_t n_challenges, eon_fr* out) {
     if (!ctx || !prog_c) return EON_E_ARG;
     auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
-    Status s = [&]() -> Status {
-        if (!zeta || !alpha || !out || (prog->width && (!local || !next)) || (n_public && !publics) ||
-            (n_challenges && !challenges))
-            return Status::err(EON_E_ARG, "null argument");
-        if (prog->ctx != ctx) return Status::err(EON_E_ARG, "program belongs to another context");
-        if ((perm_local != nullptr) != (prog->perm_width > 0) || (perm_next != nullptr) != (prog->perm_width > 0))
-            return Status::err(EON_E_ARG, prog->perm_width > 0
-                                              ? "the program reads permutation columns: perm_local and perm_next "
-                                                "must not be null"
-                                              : "the program has no permutation columns: perm_local and perm_next "
-                                                "must be null");
-        if (n_challenges != prog->n_challenges)
-            return Status::err(EON_E_SHAPE, "challenge count differs from the program's");
-        if ((pre_local != nullptr) != (prog->pre_width > 0) || (pre_next != nullptr) != (prog->pre_width > 0))
-            return Status::err(EON_E_ARG, prog->pre_width > 0
-                                              ? "the program reads preprocessed columns: pre_local and pre_next "
-                                                "must not be null"
-                                              : "the program has no preprocessed columns: pre_local and pre_next "
-                                                "must be null");
-        if (n_public != prog->n_public)
-            return Status::err(EON_E_SHAPE, "public value count differs from the program's");
+    return with_ctx(ctx, [&]() -> Status {
+        EON_TRY(check_args(ctx, prog, !zeta || !alpha || !out || (prog->width && (!local || !next)),
+                           MatArg::pair("perm_local and perm_next", perm_local, perm_next),
+                           MatArg::pair("pre_local and pre_next", pre_local, pre_next), publics, n_public, challenges,
+                           n_challenges));
         if (log_n > 28) return Status::err(EON_E_SHAPE, "log_n must be <= 28 (Fr::TWO_ADICITY)");
         const Fr al = fr_from_abi(alpha), z = fr_from_abi(zeta);
         if (!fr_is_canonical(al)) return Status::err(EON_E_ARG, "alpha is not a canonical Fr");
@@ -1562,43 +1481,24 @@ int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint3
         Fr* sels = prog->d_point.as<Fr>();
         Fr* res = sels + 4;
         EON_HIP(hipMemcpyAsync(sels, sel_host, sizeof(sel_host), hipMemcpyHostToDevice, ctx->stream));
-        RegFile regs;  // the quotient's rule, over one row
+        RegFile regs;  // over one row
         EON_TRY(plan_regs(prog, 1, &regs));
-        using KernelFn = void (*)(const CodeBlock*, uint32_t, uint32_t, const Fr*, const Fr*, const Fr*, const Fr*,
-                                  const Fr*, const Fr*, uint32_t, uint32_t, const F29*, const Fr*, Fr, Fr*, uint4*);
-        const bool has_pre = prog->pre_width > 0, has_perm = prog->perm_width > 0;
-        const KernelFn kern = regs.mode == 0 ? (has_perm  ? k_air_point<0, true, true>
-                                                : has_pre ? k_air_point<0, true, false>
-                                                          : k_air_point<0, false, false>)
-                                             : (has_perm  ? k_air_point<1, true, true>
-                                                : has_pre ? k_air_point<1, true, false>
-                                                          : k_air_point<1, false, false>);
-        if (regs.mode == 0)
-            EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        uint64_t products = 2;  // algorithmic 256-bit products: the program's, one per fold, the two results
-        for (const Instr& in : prog->code) {
-            const uint32_t opc = in.op & OP_MASK;
-            products += (opc == OP_MUL || opc == OP_SQR || opc == OP_ASSERT) ? 1 : 0;
-        }
-        ctx->prof.begin("k_air_point",
-                        2 * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32 + 6 * 32, ctx->stream,
-                        products);
-        hipLaunchKernelGGL(kern, dim3(1), dim3(regs.block), regs.shmem, ctx->stream, prog->d_code.as<CodeBlock>(),
-                           (uint32_t)((prog->code.size() + CODE_BLOCK - 1) / CODE_BLOCK), prog->n_regs,
-                           reinterpret_cast<const Fr*>(local), reinterpret_cast<const Fr*>(next),
-                           reinterpret_cast<const Fr*>(pre_local), reinterpret_cast<const Fr*>(pre_next),
-                           reinterpret_cast<const Fr*>(perm_local), reinterpret_cast<const Fr*>(perm_next),
-                           prog->width, prog->pre_width, prog->d_table.as<F29>(), sels, al, res,
-                           regs.mode == 1 ? prog->d_regs.as<uint4>() : nullptr);
-        ctx->prof.end(ctx->stream);
-        EON_HIP(hipGetLastError());
+        // products: the program's, one per fold, the two results
+        const Profile prof{"k_air_point",
+                           2 * ((uint64_t)prog->width + prog->pre_width + prog->perm_width) * 32 + 6 * 32,
+                           products(prog->code, true) + 2};
+        EON_TRY(launch_air(
+            ctx, prog, regs, 1, code_blocks(prog->code.size()), prof, prog->pre_width > 0, prog->perm_width > 0,
+            [](auto m, auto pre, auto perm) { return k_air_point<m(), pre(), perm()>; },
+            reinterpret_cast<const Fr*>(local), reinterpret_cast<const Fr*>(next),
+            reinterpret_cast<const Fr*>(pre_local), reinterpret_cast<const Fr*>(pre_next),
+            reinterpret_cast<const Fr*>(perm_local), reinterpret_cast<const Fr*>(perm_next), prog->width,
+            prog->pre_width, prog->d_table.as<F29>(), sels, al, res));
         static_assert(sizeof(Fr) == sizeof(eon_fr), "Fr is the ABI's 32 little-endian bytes");
         EON_HIP(hipMemcpyAsync(out, res, 2 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
-    }();
-    return finish(ctx, s);
+    });
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ import pytest
 
 import mirror_lookup as M
 from airs import FibonacciAir
-from airs_lookup import (LookupMockAir, LookupMultisetEqAir, RangeCheckAir, multiset_constraints,
+from airs_lookup import (LookupMockAir, LookupMultisetEqAir, RangeCheckAir, fold, multiset_constraints,
                          multiset_permuted_trace, multiset_terms, multiset_trace, range_check_constraints,
                          range_check_preprocessed, range_check_terms, range_check_trace)
 from airs_preprocessed import MulFibPAir, mul_fib_p_preprocessed, mul_fib_p_trace
@@ -238,6 +238,67 @@ def test_register_file_modes(gpu_ctx):
             outs.append(np.load(f))
     np.testing.assert_array_equal(outs[0], outs[1])
     assert outs[0].any()
+
+
+class ThreeLiveProductsAir(LookupMockAir):
+    """LookupMockAir without constraints of its own over seven main columns a, b, c, d, e, f, x and
+    one lookup of four tuples [v1 + v2 + v3], [v1 x], [v2 x], [v3 x] with v1 = a b, v2 = c d,
+    v3 = e f: the three products are computed for the first denominator and stay live until the
+    second, third and fourth read them."""
+
+    def __init__(self):
+        super().__init__([], 7, 0, 0)
+
+    def add_lookup_columns(self):
+        return [0]
+
+    def get_lookups(self):
+        from plonky3_eon_amd.symbolic import Direction, Entry, Kind, SymbolicVariable, register_lookup
+
+        a, b, c, d, e, f, x = (SymbolicVariable(Entry("main", 0), i) for i in range(7))
+        v1, v2, v3 = a * b, c * d, e * f
+        return [register_lookup(self, Kind.Local, [([v1 + v2 + v3], 1, Direction.RECEIVE), ([v1 * x], 1, Direction.SEND),
+                                                   ([v2 * x], 1, Direction.SEND), ([v3 * x], 1, Direction.SEND)])]
+
+
+def three_live_products_terms(loc, nxt, ploc, pnxt, pub, ch):
+    a, b, c, d, e, f, x = loc
+    v1, v2, v3 = a * b % P, c * d % P, e * f % P
+    return [(0, [((ch[0] - fold([(v1 + v2 + v3) % P], ch[1])) % P, 1)] +
+             [((ch[0] - fold([v * x % P], ch[1])) % P, P - 1) for v in (v1, v2, v3)])]
+
+
+def test_permutation_trace_register_file_modes(gpu_ctx):
+    """eon_lookup_permutation_dev with the term program's register file in LDS and in global memory
+    (EON_AIR_REGS, read once per process: one child process per mode) gives bit-equal permutation
+    traces, and the LDS one is the mirror's.  Registers 0 and 1 live in VGPRs, so only a term
+    program with more than two registers touches the file: ThreeLiveProductsAir's has 5, three of
+    them in memory (25 instructions; LookupMultisetEqAir's has 1 and RangeCheckAir's 2: counted
+    once by running the library's compile() on each AIR's term roots on the host).  8 rows are a
+    partial wave; 512 rows are two blocks, so the global planes' stride (the height) differs from
+    the block size."""
+    heights = (8, 512)
+    code = ("import numpy as np, torch, sys; sys.path[:0] = [sys.argv[2] + '/tests', sys.argv[2]];"
+            "from test_gpu_lookup import ThreeLiveProductsAir, rand_ints; from plonky3_eon_amd import Context;"
+            "from plonky3_eon_amd.air import AirProgram; from oracle import coracle as C;"
+            "ctx = Context(0); prog = AirProgram(ThreeLiveProductsAir(), ctx);"
+            "t = lambda n: torch.from_numpy(C.random_fr(21 + n, n * 7).reshape(n, 7, 4).view(np.int64)).to('cuda:0');"
+            "np.savez(sys.argv[1], **{str(n): prog.lookup_permutation(t(n), rand_ints(23, 2)).cpu().numpy()"
+            " for n in map(int, sys.argv[3:])})")
+    with tempfile.TemporaryDirectory() as d:
+        outs = []
+        for mode in ("lds", "global"):
+            f = os.path.join(d, mode + ".npz")
+            subprocess.run([sys.executable, "-c", code, f, str(ROOT), *map(str, heights)], check=True, timeout=300,
+                           env=dict(os.environ, EON_AIR_REGS=mode))
+            outs.append(dict(np.load(f)))
+    for n in heights:
+        lds, glob = outs[0][str(n)], outs[1][str(n)]
+        np.testing.assert_array_equal(lds, glob)
+        rows = [ints(r) for r in C.random_fr(21 + n, n * 7).reshape(n, 7, 4)]
+        want = M.generate_permutation(three_live_products_terms, rows, None, [], rand_ints(23, 2), 1)
+        assert [ints(r) for r in lds.view(np.uint64)] == want
+        assert any(any(r) for r in want)
 
 
 # ---- 4. native prove -------------------------------------------------------------------------------
