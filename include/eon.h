@@ -82,8 +82,9 @@ enum {
     EON_E_DEVICE = -3,           /* HIP runtime error */
     EON_E_OOM = -4,              /* device allocation failed */
     EON_E_ARG = -5,              /* null pointer / invalid argument */
-    EON_E_CONSTRAINT = -6        /* the prove driver's constraint check failed (eon_prove.h; the reference's
+    EON_E_CONSTRAINT = -6,       /* the prove driver's constraint check failed (eon_prove.h; the reference's
                                     debug-build panic, check_constraints.rs:165-173) */
+    EON_E_SRS = -7               /* a supplied SRS was rejected; the eon_srs_report says why */
 };
 
 enum {
@@ -246,6 +247,8 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   12: loading a supplied SRS -- eon_g1_decompress[_dev], eon_g1_validate_dev, eon_kzg_srs_check,
+ *       eon_srs_report and EON_E_SRS, additive;
  *   11: KzgMmcs -- eon_quotient_and_eval_columns_multi_dev, eon_kzg_mmcs_local_index / _open_dev /
  *       _verify_batch and eon_mmcs_matrix, additive;
  *   10: eon_air_eval_at_point_dev, the compiled constraints at one out-of-domain point, additive;
@@ -733,6 +736,66 @@ int eon_msm_sharded_dev(eon_ctx* ctx, const eon_msm_bases* bases, const eon_fr* 
  * affine, i < n.  `alpha` is a host pointer; `out` host (eon_g1_srs_powers) or device (_dev). */
 int eon_g1_srs_powers(eon_ctx* ctx, const eon_fr* alpha, uint64_t n, eon_g1_affine* out);
 int eon_g1_srs_powers_dev(eon_ctx* ctx, const eon_fr* alpha, uint64_t n, eon_g1_affine* out);
+
+/* ---- a supplied SRS (KzgPcs::from_srs, kzg/src/pcs.rs:170-175) -------------------------------
+ * The reference serialises an SRS's G1 powers as G1Affine::to_bytes (bn254/src/curve.rs:84-98):
+ * 32 bytes per point, the canonical (not Montgomery) x little-endian, bit 7 of byte 31 = the
+ * canonical y is odd, bit 6 of byte 31 = the identity.  Loading one is a square root in Fq per
+ * point, and accepting one without its trapdoor is a pairing check; both run on the device.
+ *
+ * Every check reports through an eon_srs_report: `reason` is EON_SRS_OK or why the SRS was
+ * rejected, `index` the LOWEST offending point index for the per-point reasons (ENCODING,
+ * NOT_CANONICAL, NOT_ON_CURVE, IDENTITY; when several points are bad, the reason is that point's)
+ * and 0 otherwise.  The index is a 64-bit vector atomic minimum over (index, reason) on the
+ * device, so it does not depend on scheduling.  A rejected SRS returns EON_E_SRS with the report
+ * filled; EON_OK leaves reason = EON_SRS_OK.  Other negative codes leave the report zeroed. */
+typedef struct {
+    uint32_t reason;
+    uint32_t pad;
+    uint64_t index;
+} eon_srs_report;
+enum {
+    EON_SRS_OK = 0,
+    EON_SRS_ENCODING = 1,         /* identity flag with other bits set */
+    EON_SRS_NOT_CANONICAL = 2,    /* a coordinate >= q */
+    EON_SRS_NOT_ON_CURVE = 3,     /* x^3 + 3 is no square (compressed), y^2 != x^3 + 3 (affine) */
+    EON_SRS_IDENTITY = 4,         /* an SRS power that is the point at infinity */
+    EON_SRS_G0_NOT_GENERATOR = 5, /* g1_powers[0] != G1::generator() */
+    EON_SRS_G2_INVALID = 6,       /* g2_alpha not canonical, off the twist, the identity or outside
+                                     the order-r subgroup */
+    EON_SRS_STRUCTURE = 7         /* the points are not consecutive powers of g2_alpha's scalar */
+};
+/* The exact inverse of eon_g1_to_bytes (eon_prove.h), one point per lane: `bytes` = n x 32 bytes
+ * (device, 4-byte aligned), `out` = n affine points, canonical Montgomery (device).  Per point:
+ * identity flag set -> every other bit must be zero (else ENCODING) and the output is (0,0);
+ * otherwise the flags are cleared, x >= q is NOT_CANONICAL, t = x^3 + 3, y = t^((q+1)/4) (q = 3 mod
+ * 4; one fixed 2-bit-window chain, the same for every lane), y^2 != t is NOT_ON_CURVE, and the
+ * root with the flagged parity is taken.  A rejected point is written as (0,0).  The report is
+ * read back before the call returns (it synchronizes the context's stream); n == 0 is valid.
+ * eon_g1_decompress is the same on host arrays. */
+int eon_g1_decompress_dev(eon_ctx* ctx, const uint8_t* bytes, uint64_t n, eon_g1_affine* out,
+                          eon_srs_report* report);
+int eon_g1_decompress(eon_ctx* ctx, const uint8_t* bytes, uint64_t n, eon_g1_affine* out, eon_srs_report* report);
+/* Uncompressed SRS powers (device): both coordinates < q (else NOT_CANONICAL), not (0,0)
+ * (IDENTITY), y^2 = x^3 + 3 (else NOT_ON_CURVE).  G1 has cofactor 1, so on the curve is in the
+ * group.  Synchronous like eon_g1_decompress_dev. */
+int eon_g1_validate_dev(eon_ctx* ctx, const eon_g1_affine* pts, uint64_t n, eon_srs_report* report);
+/* Accept bases[0..n) with g2_alpha as an SRS without knowing alpha (n >= 1, n <= the bases' length):
+ *   1. bases[0] == G1::generator(), else G0_NOT_GENERATOR;
+ *   2. g2_alpha canonical, on the twist, not the identity and [r - 1] Q == -Q (eon_g2_mul's plain
+ *      double-and-add with complete case handling: it assumes nothing about Q's order), else
+ *      G2_INVALID;
+ *   3. for n > 1, with A = sum_{i<n-1} rho^i G_i and B = sum_{i<n-1} rho^i G_(i+1) -- both from ONE
+ *      column MSM (eon_msm_g1_columns_dev's) over the bases' own tables, of the n x 2 matrix with
+ *      columns (rho^0 .. rho^(n-2), 0) and (0, rho^0 .. rho^(n-2)) built on the device --
+ *      e(A, g2_alpha) e(-B, G2) == 1 through eon_multi_pairing, else STRUCTURE.
+ * If G_(i+1) != alpha G_i for some i the check passes only when rho is a root of a nonzero
+ * polynomial of degree < n: a chance below n / r for a uniformly random rho, which the caller
+ * must draw AFTER the SRS is fixed.  rho (host, Montgomery ABI form) zero or not canonical is
+ * EON_E_ARG.  The per-point checks above are the caller's (the MSM needs curve points).  Host
+ * outputs, synchronous. */
+int eon_kzg_srs_check(eon_ctx* ctx, const eon_msm_bases* bases, uint64_t n, const eon_g2_affine* g2_alpha,
+                      const eon_fr* rho, eon_srs_report* report);
 
 /* ---- verifier pairings (setup / verify, not prove time) --------------------
  * All host pointers, synchronous.  G1 / G2 inputs must be canonical and on their curves

@@ -41,6 +41,33 @@ typedef struct eon_kzg_pcs eon_kzg_pcs;
 /* KzgPcs::new(max_degree, alpha): SRS g1_powers[0..=max_degree] generated and kept on device as
  * fixed-base MSM bases (alpha is a host pointer). */
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out);
+/* KzgPcs::from_srs(StructuredReferenceString) (kzg/src/pcs.rs:170-175): a prover and verifier over a
+ * SUPPLIED SRS, without its trapdoor.  g1_powers = n host affine points (eon_kzg_pcs_create_from_srs)
+ * or n x 32 compressed bytes, G1Affine::to_bytes each (eon_kzg_pcs_create_from_srs_bytes);
+ * max_degree = n - 1 (n == 0 is EON_E_ARG); g2_alpha is kept as given and no alpha is known.  In
+ * order: upload; per point, eon_g1_decompress_dev (bytes only) and eon_g1_validate_dev -- always, they
+ * cost far less than the tables; eon_msm_bases_create_dev(EON_MSM_PRECOMPUTE); eon_kzg_srs_check with
+ * `rho` (host, a nonzero canonical Fr the caller draws uniformly AFTER the SRS is fixed), unless flags
+ * has EON_SRS_TRUSTED -- the caller vouches for the SRS (its own file, checked before), rho may then
+ * be NULL and a table that is no SRS is accepted.  On a rejected SRS the call returns EON_E_SRS,
+ * *report (eon.h) says why, nothing is kept and *out is untouched.  The device state of a handle made
+ * from the powers of alpha is byte for byte that of eon_kzg_pcs_create(max_degree, alpha), so its
+ * proofs are too. */
+enum {
+    EON_SRS_TRUSTED = 1
+};
+int eon_kzg_pcs_create_from_srs(eon_ctx* ctx, const eon_g1_affine* g1_powers, uint64_t n,
+                                const eon_g2_affine* g2_alpha, uint32_t flags, const eon_fr* rho,
+                                eon_kzg_pcs** out, eon_srs_report* report);
+int eon_kzg_pcs_create_from_srs_bytes(eon_ctx* ctx, const uint8_t* g1_bytes, uint64_t n,
+                                      const eon_g2_affine* g2_alpha, uint32_t flags, const eon_fr* rho,
+                                      eon_kzg_pcs** out, eon_srs_report* report);
+/* The verifier's half: max_degree and g2_alpha, no G1 table (the verifier reads neither).
+ * eon_verify_air[_fs] work on the handle; every prove and setup entry point returns EON_E_ARG and
+ * eon_kzg_pcs_last_error says the handle is verifier-only.  g2_alpha is taken as given: it comes from
+ * an SRS that eon_kzg_pcs_create_from_srs (or the party that made it) has checked. */
+int eon_kzg_pcs_create_verifier(eon_ctx* ctx, uint64_t max_degree, const eon_g2_affine* g2_alpha,
+                                eon_kzg_pcs** out);
 void eon_kzg_pcs_destroy(eon_kzg_pcs* pcs);
 /* message of the last failing call on this pcs (driver-side errors and eon.h errors) */
 const char* eon_kzg_pcs_last_error(const eon_kzg_pcs* pcs);
@@ -318,7 +345,8 @@ int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_p
                       eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out);
 
 /* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
- * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; all additive) */
+ * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; 8:
+ * eon_kzg_pcs_create_from_srs[_bytes] and eon_kzg_pcs_create_verifier; all additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

@@ -19,12 +19,21 @@ EON_E_DEVICE = -3
 EON_E_OOM = -4
 EON_E_ARG = -5
 EON_E_CONSTRAINT = -6
+EON_E_SRS = -7
+EON_SRS_OK = 0
+EON_SRS_ENCODING = 1
+EON_SRS_NOT_CANONICAL = 2
+EON_SRS_NOT_ON_CURVE = 3
+EON_SRS_IDENTITY = 4
+EON_SRS_G0_NOT_GENERATOR = 5
+EON_SRS_G2_INVALID = 6
+EON_SRS_STRUCTURE = 7
 EON_ORDER_NATURAL = 0
 EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 11  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 12  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -33,6 +42,7 @@ _ERRNAMES = {
     EON_E_OOM: "EON_E_OOM",
     EON_E_ARG: "EON_E_ARG",
     EON_E_CONSTRAINT: "EON_E_CONSTRAINT",
+    EON_E_SRS: "EON_E_SRS",
 }
 
 
@@ -74,6 +84,10 @@ class eon_air_program_stats(ctypes.Structure):
 class eon_constraint_report(ctypes.Structure):
     _fields_ = [("failures", ctypes.c_uint64), ("row", ctypes.c_uint64), ("constraint", ctypes.c_uint32),
                 ("failing_constraints", ctypes.c_uint32), ("value", eon_fr)]
+
+
+class eon_srs_report(ctypes.Structure):
+    _fields_ = [("reason", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("index", ctypes.c_uint64)]
 
 
 class eon_clock_probe(ctypes.Structure):
@@ -165,6 +179,10 @@ SIGNATURES = {
     "eon_multi_pairing": (_INT, [_P, _P, _P, _U64, _P]),
     "eon_kzg_verify_batch": (_INT, [_P, _P, _P, _P, _P, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
     "eon_g1_srs_powers_dev": (_INT, [_P, _P, _U64, _P]),
+    "eon_g1_decompress_dev": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
+    "eon_g1_decompress": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
+    "eon_g1_validate_dev": (_INT, [_P, _P, _U64, ctypes.POINTER(eon_srs_report)]),
+    "eon_kzg_srs_check": (_INT, [_P, _P, _U64, _P, _P, ctypes.POINTER(eon_srs_report)]),
     "eon_selectors_on_coset_dev": (_INT, [_P, _U32, _U32, _P, _P]),
     "eon_p2air_create": (_INT, [_P, _P, _U32, ctypes.POINTER(_P)]),
     "eon_p2air_destroy": (None, [_P]),

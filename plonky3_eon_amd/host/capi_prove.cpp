@@ -75,7 +75,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 7; }
+uint32_t eon_prove_abi_version(void) { return 8; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -83,6 +83,49 @@ int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alph
     const int rc = guarded(h, [&] {
         h->pcs = new eon_host::KzgPcs(ctx, max_degree, eon_host::Fr::from_abi(*srs_alpha));
     });
+    if (rc != EON_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return EON_OK;
+}
+
+static int create_from_srs(eon_ctx* ctx, const void* g1_powers, bool compressed, uint64_t n,
+                           const eon_g2_affine* g2_alpha, uint32_t flags, const eon_fr* rho, eon_kzg_pcs** out,
+                           eon_srs_report* report) {
+    if (!ctx || !g1_powers || !n || !g2_alpha || !out || !report) return EON_E_ARG;
+    if (!rho && !(flags & EON_SRS_TRUSTED)) return EON_E_ARG;
+    *report = eon_srs_report{};
+    eon_kzg_pcs* h = new eon_kzg_pcs();
+    const int rc = guarded(h, [&] {
+        h->pcs = new eon_host::KzgPcs(ctx, g1_powers, compressed, n, *g2_alpha, flags, rho, report);
+    });
+    if (rc != EON_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return EON_OK;
+}
+
+int eon_kzg_pcs_create_from_srs(eon_ctx* ctx, const eon_g1_affine* g1_powers, uint64_t n,
+                                const eon_g2_affine* g2_alpha, uint32_t flags, const eon_fr* rho,
+                                eon_kzg_pcs** out, eon_srs_report* report) {
+    return create_from_srs(ctx, g1_powers, false, n, g2_alpha, flags, rho, out, report);
+}
+
+int eon_kzg_pcs_create_from_srs_bytes(eon_ctx* ctx, const uint8_t* g1_bytes, uint64_t n,
+                                      const eon_g2_affine* g2_alpha, uint32_t flags, const eon_fr* rho,
+                                      eon_kzg_pcs** out, eon_srs_report* report) {
+    return create_from_srs(ctx, g1_bytes, true, n, g2_alpha, flags, rho, out, report);
+}
+
+int eon_kzg_pcs_create_verifier(eon_ctx* ctx, uint64_t max_degree, const eon_g2_affine* g2_alpha,
+                                eon_kzg_pcs** out) {
+    if (!ctx || !g2_alpha || !out) return EON_E_ARG;
+    eon_kzg_pcs* h = new eon_kzg_pcs();
+    const int rc = guarded(h, [&] { h->pcs = new eon_host::KzgPcs(ctx, max_degree, *g2_alpha); });
     if (rc != EON_OK) {
         delete h;
         return rc;

@@ -1,6 +1,8 @@
 // KzgPcs over eon.h (see pcs.h).  Reference: kzg/src/pcs.rs, commit/src/{pcs,domain}.rs.
 #include "pcs.h"
 
+#include "eon_prove.h"
+
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -147,6 +149,51 @@ KzgPcs::KzgPcs(eon_ctx* ctx, uint64_t max_degree, const Fr& srs_alpha)
     check(ctx_, eon_msm_bases_create_dev(ctx_, pts.as<eon_g1_affine>(), n, EON_MSM_PRECOMPUTE, &bases_),
           "eon_msm_bases_create_dev");
     check(ctx_, eon_ctx_synchronize(ctx_), "eon_ctx_synchronize");
+    init_aux();
+}
+
+KzgPcs::KzgPcs(eon_ctx* ctx, const void* g1_powers, bool compressed, uint64_t n, const eon_g2_affine& g2_alpha,
+               uint32_t flags, const eon_fr* rho, eon_srs_report* report)
+    : ctx_(ctx), max_degree_(n - 1), have_g2_alpha_(true), g2_alpha_(g2_alpha) {
+    hipStream_t st = static_cast<hipStream_t>(eon_ctx_stream(ctx_));
+    DeviceBuffer pts(n * sizeof(eon_g1_affine));
+    if (compressed) {
+        DeviceBuffer raw(n * 32);
+        hip_check(hipMemcpyAsync(raw.get(), g1_powers, n * 32, hipMemcpyHostToDevice, st), "SRS upload");
+        check(ctx_, eon_g1_decompress_dev(ctx_, raw.as<uint8_t>(), n, pts.as<eon_g1_affine>(), report),
+              "eon_g1_decompress_dev");
+    } else {
+        hip_check(hipMemcpyAsync(pts.get(), g1_powers, n * sizeof(eon_g1_affine), hipMemcpyHostToDevice, st),
+                  "SRS upload");
+    }
+    // always: far cheaper than the tables, and the MSM's formulas need curve points (for compressed
+    // input it is what rejects an encoded identity)
+    check(ctx_, eon_g1_validate_dev(ctx_, pts.as<eon_g1_affine>(), n, report), "eon_g1_validate_dev");
+    check(ctx_, eon_msm_bases_create_dev(ctx_, pts.as<eon_g1_affine>(), n, EON_MSM_PRECOMPUTE, &bases_),
+          "eon_msm_bases_create_dev");
+    try {  // a constructor that throws runs no destructor: the tables go here
+        if (!(flags & EON_SRS_TRUSTED)) {
+            if (!rho) throw Error(EON_E_ARG, "rho is required unless EON_SRS_TRUSTED is set");
+            check(ctx_, eon_kzg_srs_check(ctx_, bases_, n, &g2_alpha_, rho, report), "eon_kzg_srs_check");
+        }
+        check(ctx_, eon_ctx_synchronize(ctx_), "eon_ctx_synchronize");
+    } catch (...) {
+        eon_msm_bases_destroy(bases_);
+        bases_ = nullptr;
+        throw;
+    }
+    init_aux();
+}
+
+KzgPcs::KzgPcs(eon_ctx* ctx, uint64_t max_degree, const eon_g2_affine& g2_alpha)
+    : ctx_(ctx), max_degree_(max_degree), have_g2_alpha_(true), g2_alpha_(g2_alpha) {}
+
+void KzgPcs::require_prover(const char* what) const {
+    if (!bases_)
+        throw Error(EON_E_ARG, std::string(what) + ": this KzgPcs is a verifier-only handle (no G1 powers)");
+}
+
+void KzgPcs::init_aux() {
     // the auxiliary context: its own non-blocking stream, so that its work overlaps this
     // context's even when that one runs on the legacy null stream
     const int dev = eon_ctx_device(ctx_);
@@ -190,6 +237,7 @@ const eon_g2_affine& KzgPcs::g2_alpha() {
 
 void KzgPcs::commit_coeffs(std::vector<std::pair<Domain, DeviceMatrix>> evaluations,
                            std::vector<MatrixProverData>& data) {
+    require_prover("commit");
     for (auto& [domain, evals] : evaluations) {
         const uint64_t h = evals.height;
         const uint32_t w = evals.width;
@@ -206,6 +254,7 @@ void KzgPcs::commit_coeffs(std::vector<std::pair<Domain, DeviceMatrix>> evaluati
 
 void KzgPcs::commit_columns(std::vector<MatrixProverData>& data, size_t first,
                             std::vector<std::vector<eon_g1_affine>>& commitments) {
+    require_prover("commit");
     for (size_t k = first; k < data.size(); k++) {
         MatrixProverData& d = data[k];
         const uint64_t h = d.coeffs.height;
@@ -270,6 +319,7 @@ void KzgPcs::commit_quotient(const Domain& quotient_domain, const DeviceMatrix& 
 }
 
 std::vector<Opened> KzgPcs::open(const std::vector<OpenRound>& rounds) {
+    require_prover("open");
     for (const OpenRound& r : rounds) {
         if (r.data->size() != r.points.size()) throw Error(EON_E_SHAPE, "one point list per matrix");
         for (const MatrixProverData& m : *r.data)

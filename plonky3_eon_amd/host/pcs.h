@@ -103,6 +103,16 @@ struct OpenRound {
 class KzgPcs {
   public:
     KzgPcs(eon_ctx* ctx, uint64_t max_degree, const Fr& srs_alpha);
+    // KzgPcs::from_srs (pcs.rs:170-175): a supplied SRS, n = max_degree + 1 G1 powers on the host as
+    // affine points (compressed == false) or as n x 32 compressed bytes, and g2_alpha as given; no
+    // alpha is known or kept.  Upload, per-point decompression and validation on the device, the
+    // fixed-base tables, then eon_kzg_srs_check with `rho` unless flags has EON_SRS_TRUSTED.  A
+    // rejected SRS throws Error(EON_E_SRS) with *report filled; nothing is kept.
+    KzgPcs(eon_ctx* ctx, const void* g1_powers, bool compressed, uint64_t n, const eon_g2_affine& g2_alpha,
+           uint32_t flags, const eon_fr* rho, eon_srs_report* report);
+    // The verifier's half of the SRS (g2_alpha and max_degree): no G1 table is built, verify works,
+    // every commit / open throws Error(EON_E_ARG).
+    KzgPcs(eon_ctx* ctx, uint64_t max_degree, const eon_g2_affine& g2_alpha);
     ~KzgPcs();
     KzgPcs(const KzgPcs&) = delete;
     KzgPcs& operator=(const KzgPcs&) = delete;
@@ -140,13 +150,17 @@ class KzgPcs {
     // must come from commit / commit_columns (which keep those digits); otherwise EON_E_ARG.
     std::vector<Opened> open(const std::vector<OpenRound>& rounds);
     // init_srs_unsafe's g2_alpha = [alpha] G2 (params.rs:123-139), the verifier's half of the SRS:
-    // made by eon_g2_mul at the first verify and kept
+    // made by eon_g2_mul at the first verify and kept; a supplied SRS's own otherwise
     const eon_g2_affine& g2_alpha();
+    bool verifier_only() const { return !bases_; }
+    // Error(EON_E_ARG) on a verifier-only handle
+    void require_prover(const char* what) const;
 
   private:
+    void init_aux();
     eon_ctx* ctx_;
     uint64_t max_degree_;
-    Fr srs_alpha_;
+    Fr srs_alpha_ = Fr::zero();
     bool have_g2_alpha_ = false;
     eon_g2_affine g2_alpha_{};
     eon_msm_bases* bases_ = nullptr;

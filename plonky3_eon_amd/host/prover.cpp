@@ -59,6 +59,7 @@ uint32_t AirRef::width() const {
 
 std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_trace, uint64_t height,
                                                  uint32_t width) {
+    pcs.require_prover("setup_preprocessed");
     eon_ctx* ctx = pcs.ctx();
     if (width == 0)  // preprocessed.rs:68-70 returns None: the caller proves without one
         throw Error(EON_E_SHAPE, "the preprocessed trace has no columns: prove without preprocessed data");
@@ -87,6 +88,7 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
             const Fr& zeta_in, uint32_t max_constraint_degree, const eon_collective* shard,
             DuplexChallenger* challenger, const Preprocessed* pp, const LookupInputs* lookups,
             ConstraintCheck* constraint_check) {
+    pcs.require_prover("prove");
     eon_ctx* ctx = pcs.ctx();
     using clock = std::chrono::steady_clock;
     auto tick = [&] {

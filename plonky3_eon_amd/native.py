@@ -35,6 +35,7 @@ _INT = ctypes.c_int
 STAGES = ["commit to trace data", "trace LDE (get_evaluations_on_domain)", "quotient_values",
           "exchange partial quotients", "commit to quotient poly chunks", "open", "assemble columns"]
 EON_STAGES = 8
+EON_SRS_TRUSTED = 1  # eon_kzg_pcs_create_from_srs flags: skip eon_kzg_srs_check
 
 class eon_proof(ctypes.Structure):
     _fields_ = [("trace_commit", _P), ("quotient_commit", _P), ("trace_opened", _P), ("trace_witnesses", _P),
@@ -56,6 +57,11 @@ class eon_proof_lk(ctypes.Structure):
 SIGNATURES = {
     "eon_prove_abi_version": (_U32, []),
     "eon_kzg_pcs_create": (_INT, [_P, _U64, _P, ctypes.POINTER(_P)]),
+    "eon_kzg_pcs_create_from_srs": (_INT, [_P, _P, _U64, _P, _U32, _P, ctypes.POINTER(_P),
+                                           ctypes.POINTER(_lib.eon_srs_report)]),
+    "eon_kzg_pcs_create_from_srs_bytes": (_INT, [_P, _P, _U64, _P, _U32, _P, ctypes.POINTER(_P),
+                                                 ctypes.POINTER(_lib.eon_srs_report)]),
+    "eon_kzg_pcs_create_verifier": (_INT, [_P, _U64, _P, ctypes.POINTER(_P)]),
     "eon_kzg_pcs_destroy": (None, [_P]),
     "eon_kzg_pcs_last_error": (ctypes.c_char_p, [_P]),
     "eon_kzg_pcs_set_check_constraints": (_INT, [_P, _INT]),
@@ -138,6 +144,64 @@ class NativeKzgPcs:
         a = fr_to_abi(alpha)
         self.ctx.check(self.lib.eon_kzg_pcs_create(self.ctx.handle, max_degree, ctypes.byref(a), ctypes.byref(h)))
         self._h = h
+
+    @classmethod
+    def from_srs(cls, srs, validate: bool = True, rho: int | None = None,
+                 ctx: Context | None = None) -> "NativeKzgPcs":
+        """KzgPcs::from_srs (kzg/src/pcs.rs:170-175) over a supplied srs.Srs, affine or compressed:
+        eon_kzg_pcs_create_from_srs[_bytes].  Every point is decompressed / validated on the device;
+        with `validate` the SRS is also checked against its g2_alpha (eon_kzg_srs_check) with the
+        challenge `rho`, by default drawn here, after the SRS is fixed, from the OS's randomness.
+        validate=False is EON_SRS_TRUSTED: the caller vouches for the table.  Raises srs.SrsError
+        (reason, index) when the SRS is rejected."""
+        import secrets
+
+        from .field import FR_MODULUS
+        from .srs import SrsError
+
+        self = cls.__new__(cls)
+        self.ctx = ctx or default_context(0)
+        self.lib = load()
+        self.max_degree = srs.max_degree
+        self._h = None
+        flags = 0 if validate else EON_SRS_TRUSTED
+        r = None
+        if validate:
+            r = fr_to_abi(int(rho) if rho is not None else secrets.randbelow(FR_MODULUS - 1) + 1)
+        g2 = np.ascontiguousarray(srs.g2_alpha, dtype=np.uint64).reshape(16)
+        rep = _lib.eon_srs_report()
+        h = ctypes.c_void_p()
+        self.ctx.set_stream(None)
+        if srs.compressed:
+            buf = np.zeros(srs.n * 4, dtype=np.uint64)  # word-aligned staging of the bytes
+            buf.view(np.uint8)[:] = np.frombuffer(srs.g1_bytes, dtype=np.uint8)
+            rc = self.lib.eon_kzg_pcs_create_from_srs_bytes(self.ctx.handle, _p(buf), srs.n, _p(g2), flags,
+                                                            ctypes.byref(r) if r is not None else None,
+                                                            ctypes.byref(h), ctypes.byref(rep))
+        else:
+            pts = np.ascontiguousarray(srs.g1_powers, dtype=np.uint64)
+            rc = self.lib.eon_kzg_pcs_create_from_srs(self.ctx.handle, _p(pts), srs.n, _p(g2), flags,
+                                                      ctypes.byref(r) if r is not None else None,
+                                                      ctypes.byref(h), ctypes.byref(rep))
+        if rc == _lib.EON_E_SRS:
+            raise SrsError(int(rep.reason), int(rep.index))
+        self.ctx.check(rc)
+        self._h = h
+        return self
+
+    @classmethod
+    def verifier(cls, max_degree: int, g2_alpha, ctx: Context | None = None) -> "NativeKzgPcs":
+        """eon_kzg_pcs_create_verifier: the verifier's half of an SRS (max_degree and g2_alpha), no
+        G1 table.  verify_native works on it; every prove and setup raises EonError(EON_E_ARG)."""
+        self = cls.__new__(cls)
+        self.ctx = ctx or default_context(0)
+        self.lib = load()
+        self.max_degree = int(max_degree)
+        g2 = np.ascontiguousarray(g2_alpha, dtype=np.uint64).reshape(16)
+        h = ctypes.c_void_p()
+        self.ctx.check(self.lib.eon_kzg_pcs_create_verifier(self.ctx.handle, self.max_degree, _p(g2), ctypes.byref(h)))
+        self._h = h
+        return self
 
     def check(self, rc: int):
         if rc == _lib.EON_E_CONSTRAINT:
