@@ -247,6 +247,7 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   13: eon_fr_fold_columns_dev, the gamma-fold of the batched KZG opening, additive;
  *   12: loading a supplied SRS -- eon_g1_decompress[_dev], eon_g1_validate_dev, eon_kzg_srs_check,
  *       eon_srs_report and EON_E_SRS, additive;
  *   11: KzgMmcs -- eon_quotient_and_eval_columns_multi_dev, eon_kzg_mmcs_local_index / _open_dev /
@@ -698,6 +699,19 @@ int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog, uint32_
  * shards' partial quotients and weights shard g by alpha^(K_lane * (VECTOR_LEN - lane_end_g)). */
 int eon_fr_lincomb_dev(eon_ctx* ctx, const eon_fr* in, uint32_t k, uint64_t rows,
                        const eon_fr* coeffs, eon_fr* out);
+
+/* out[i] = scale * sum_{j<width} gamma^j * mat[i*width + j] (device mat/out, host gamma/scale): the
+ * gamma-fold of a row-major rows x width matrix into one column, F = sum_j gamma^j f_j of the
+ * batched KZG opening (eon_prove.h, EON_OPENING_BATCHED).  scale NULL = one.  out is canonical and
+ * must not overlap mat (EON_E_ARG).  gamma and scale follow `point` of eon_eval_columns_dev: host
+ * pointers to canonical Fr, EON_E_ARG otherwise.  width == 1 is a (scaled) copy; rows == 0 writes
+ * nothing; width == 0 writes rows zeros.  A NULL pointer that would be read or written is EON_E_ARG.
+ * Any width runs (a wave walks its row in 64-column tiles; 9168, the Blake3-AIR's, is 144 of them):
+ * there is no upper limit short of rows * width * 32 overflowing 64 bits (EON_E_SHAPE).  The powers
+ * gamma^0..gamma^63 are made on the device per call as Shoup constants; asynchronous on the
+ * context's stream. */
+int eon_fr_fold_columns_dev(eon_ctx* ctx, const eon_fr* mat, uint64_t rows, uint32_t width,
+                            const eon_fr* gamma, const eon_fr* scale, eon_fr* out);
 
 /* ---- four-step NTT across ranks (BASELINE configs[4]) ------------------------
  * Step 2 + the local half of step 3 of a size-2^log_n forward DFT split as N1 x N2

@@ -98,6 +98,46 @@ int eon_kzg_pcs_set_check_constraints(eon_kzg_pcs* pcs, int enable);
 int eon_kzg_pcs_check_constraints(const eon_kzg_pcs* pcs); /* 1 / 0 */
 int eon_kzg_pcs_last_constraint_report(const eon_kzg_pcs* pcs, eon_constraint_report* out);
 
+/* ---- the opening mode ---------------------------------------------------------------------------
+ * EON_OPENING_PER_COLUMN (the default) is the reference's KzgPcs::open: one witness per opened
+ * column and point, and a verify that multiplies all pairing checks WITHOUT random weights, as the
+ * reference's verify_batch does (kzg/src/util.rs:245-292) -- restated faithfully, and as a batch
+ * check not sound.  With the mode at its default every prove and verify is byte for byte and launch
+ * for launch what it is without this surface.
+ *
+ * EON_OPENING_BATCHED is the standard batched KZG opening, NOT the reference's KzgProof: a matrix's
+ * columns are folded with powers of a challenge gamma, F = sum_j gamma^j f_j
+ * (eon_fr_fold_columns_dev), F is opened once per point, W = commit_column(quotient_and_eval(F, z).0),
+ * and the claims are combined with a second challenge delta.  Commitments and opened values are laid
+ * out as in the per-column mode; the witness arrays are compact: trace_witnesses,
+ * permutation_witnesses and preprocessed_witnesses hold [2] points (zeta, zeta h) and
+ * quotient_witnesses stays [C] (a width-1 matrix is its own fold: those witnesses equal the
+ * per-column ones bit for bit).  Every unsharded eon_prove_* entry writes them so; a collective with
+ * world > 1 in this mode is EON_E_ARG.
+ *   Claims i = 0..K-1, in the reference's round order: trace zeta, trace zeta h; [permutation zeta,
+ *   zeta h]; chunk 0..C-1 at zeta; [preprocessed zeta, zeta h].
+ *   Transcript (_fs forms): unchanged up to zeta -- alpha, zeta, all commitments and all opened values
+ *   equal the per-column proof's; then every opened value is observed in claim order, column by
+ *   column; gamma is sampled; the K witnesses are observed in claim order (observe_g1); delta is
+ *   sampled.  Prover and verifier both do this: their challengers end in the same state.
+ *   Fixed-challenge forms take gamma and delta from eon_kzg_pcs_set_opening_challenges (host,
+ *   canonical Fr, copied; NULL clears one): the prover needs gamma, the verifier both; a missing one
+ *   is EON_E_ARG.
+ *   eon_verify_air[_fs]: shape checks as in the per-column mode; per claim C_i = sum_j gamma^j C_(m,j)
+ *   and v_i = sum_j gamma^j v_(i,j); ONE eon_kzg_verify_batch on (delta^i C_i, delta^i W_i,
+ *   delta^i v_i, z_i), i.e. prod_i e(delta^i (C_i - v_i G1), G2) e(-delta^i W_i, g2_alpha - z_i G2)
+ *   = 1, every scaled point from ONE variable-base column MSM (eon_msm_g1_columns) over the proof's
+ *   commitments and witnesses.  A failure, or a commitment or
+ *   witness that is no curve point, is EON_VERIFY_INVALID_OPENING_ARGUMENT.
+ * eon_kzg_pcs_last_opening_challenges: the gamma and delta of the last batched prove or verify on
+ * this pcs (either pointer may be NULL; a fixed-challenge prove reports the delta that was set, or
+ * zero); EON_E_ARG when none has run. */
+enum { EON_OPENING_PER_COLUMN = 0, EON_OPENING_BATCHED = 1 };
+int eon_kzg_pcs_set_opening(eon_kzg_pcs* pcs, uint32_t mode);
+int eon_kzg_pcs_opening(const eon_kzg_pcs* pcs); /* the mode */
+int eon_kzg_pcs_set_opening_challenges(eon_kzg_pcs* pcs, const eon_fr* gamma, const eon_fr* delta);
+int eon_kzg_pcs_last_opening_challenges(const eon_kzg_pcs* pcs, eon_fr* gamma, eon_fr* delta);
+
 /* Lane-sharded prove: this rank's share of VECTOR_LEN and an all-gather over
  * DEVICE buffers (eon_collective, declared in eon.h). */
 
@@ -131,7 +171,10 @@ enum {
 };
 
 /* Proof fields (eon-uni-stark/src/proof.rs:19-44), caller-allocated host arrays; W is the FULL
- * trace width (164 * VECTOR_LEN over all ranks), C = 2^log_qd quotient chunks (2 for degree 3). */
+ * trace width (164 * VECTOR_LEN over all ranks), C = 2^log_qd quotient chunks (2 for degree 3).
+ * In the batched opening mode (EON_OPENING_BATCHED, above) trace_witnesses -- and the
+ * preprocessed_witnesses / permutation_witnesses of the structs below -- hold [2] points, one per
+ * opened point; every other array is as given here. */
 typedef struct {
     eon_g1_affine* trace_commit;       /* [W] */
     eon_g1_affine* quotient_commit;    /* [C] */
@@ -346,7 +389,8 @@ int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_p
 
 /* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
  * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; 8:
- * eon_kzg_pcs_create_from_srs[_bytes] and eon_kzg_pcs_create_verifier; all additive) */
+ * eon_kzg_pcs_create_from_srs[_bytes] and eon_kzg_pcs_create_verifier; 9: the opening mode,
+ * eon_kzg_pcs_set_opening and its challenges; all additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

@@ -33,7 +33,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 12  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 13  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -215,6 +215,7 @@ SIGNATURES = {
     "eon_check_constraints_dev": (_INT, [_P, _P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P, _P]),
     "eon_air_eval_at_point_dev": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _U32, _P]),
     "eon_fr_lincomb_dev": (_INT, [_P, _P, _U32, _U64, _P, _P]),
+    "eon_fr_fold_columns_dev": (_INT, [_P, _P, _U64, _U32, _P, _P, _P]),
     "eon_fourstep_twiddle_pack_dev": (_INT, [_P, _P, _U32, _U32, _U64, _U32, _U32, _P]),
 }
 

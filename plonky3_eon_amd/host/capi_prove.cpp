@@ -13,6 +13,11 @@ struct eon_kzg_pcs {
     std::string last_error;
     bool check_constraints = false;        // eon_kzg_pcs_set_check_constraints
     eon_constraint_report last_report{};   // of the last eon_prove_air* that ran with the switch on
+    uint32_t opening = EON_OPENING_PER_COLUMN;  // eon_kzg_pcs_set_opening
+    bool have_gamma = false, have_delta = false;  // eon_kzg_pcs_set_opening_challenges
+    eon_host::Fr gamma = eon_host::Fr::zero(), delta = eon_host::Fr::zero();
+    bool have_last = false;  // of the last batched prove / verify
+    eon_host::Fr last_gamma = eon_host::Fr::zero(), last_delta = eon_host::Fr::zero();
 };
 
 struct eon_preprocessed {
@@ -54,6 +59,33 @@ int guarded_prove(eon_kzg_pcs* h, F&& f) {
     return rc;
 }
 
+// The pcs's opening mode for one prove: get() is null in the per-column mode, so that prove is then
+// what it is without this surface; done() records the challenges a batched prove used (delta: the
+// transcript's with a challenger, else the one set on the pcs, else zero).
+struct OpeningScope {
+    eon_kzg_pcs* h;
+    eon_host::BatchedOpening bo;
+    explicit OpeningScope(eon_kzg_pcs* h_) : h(h_) {
+        bo.have_gamma = h->have_gamma;
+        bo.gamma = h->gamma;
+    }
+    eon_host::BatchedOpening* get() { return h->opening == EON_OPENING_BATCHED ? &bo : nullptr; }
+    void done(bool fs) {
+        if (h->opening != EON_OPENING_BATCHED) return;
+        h->have_last = true;
+        h->last_gamma = bo.gamma_used;
+        h->last_delta = fs ? bo.delta_used : h->have_delta ? h->delta : eon_host::Fr::zero();
+    }
+};
+
+bool canonical(const eon_fr& v) {
+    for (int k = 3; k >= 0; k--) {
+        if (v.l[k] < eon_host::Fr::P[k]) return true;
+        if (v.l[k] > eon_host::Fr::P[k]) return false;
+    }
+    return false;
+}
+
 void copy_out(const eon_host::Proof& p, eon_proof* out);
 void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out);
 void copy_out_lk(const eon_host::Proof& p, eon_proof_lk* out);
@@ -75,7 +107,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 8; }
+uint32_t eon_prove_abi_version(void) { return 9; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -156,6 +188,30 @@ int eon_kzg_pcs_last_constraint_report(const eon_kzg_pcs* pcs, eon_constraint_re
     return EON_OK;
 }
 
+int eon_kzg_pcs_set_opening(eon_kzg_pcs* pcs, uint32_t mode) {
+    if (!pcs || (mode != EON_OPENING_PER_COLUMN && mode != EON_OPENING_BATCHED)) return EON_E_ARG;
+    pcs->opening = mode;
+    return EON_OK;
+}
+
+int eon_kzg_pcs_opening(const eon_kzg_pcs* pcs) { return pcs ? (int)pcs->opening : EON_E_ARG; }
+
+int eon_kzg_pcs_set_opening_challenges(eon_kzg_pcs* pcs, const eon_fr* gamma, const eon_fr* delta) {
+    if (!pcs || (gamma && !canonical(*gamma)) || (delta && !canonical(*delta))) return EON_E_ARG;
+    pcs->have_gamma = gamma != nullptr;
+    pcs->have_delta = delta != nullptr;
+    if (gamma) pcs->gamma = eon_host::Fr::from_abi(*gamma);
+    if (delta) pcs->delta = eon_host::Fr::from_abi(*delta);
+    return EON_OK;
+}
+
+int eon_kzg_pcs_last_opening_challenges(const eon_kzg_pcs* pcs, eon_fr* gamma, eon_fr* delta) {
+    if (!pcs || !pcs->have_last) return EON_E_ARG;
+    if (gamma) *gamma = pcs->last_gamma.abi();
+    if (delta) *delta = pcs->last_delta.abi();
+    return EON_OK;
+}
+
 int eon_poseidon2_bn254_permute(const eon_poseidon2_constants* perm, eon_fr state[3]) {
     if (!perm || !state) return EON_E_ARG;
     return guarded(nullptr, [&] {
@@ -225,8 +281,10 @@ int eon_prove_p2air(eon_kzg_pcs* pcs, const eon_p2air* air, const eon_fr* trace,
         using namespace eon_host;
         AirRef a;
         a.p2 = air;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta),
-                        max_constraint_degree, shard);
+                        max_constraint_degree, shard, nullptr, nullptr, nullptr, nullptr, os.get());
+        os.done(false);
         copy_out(p, out);
     });
 }
@@ -245,8 +303,10 @@ int eon_prove_air(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* t
         a.prog = prog;
         a.publics = publics;
         a.n_public = n_public;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
-                        nullptr, nullptr, cc);
+                        nullptr, nullptr, cc, os.get());
+        os.done(false);
         copy_out(p, out);
     });
 }
@@ -264,8 +324,10 @@ int eon_prove_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
         a.prog = prog;
         a.publics = publics;
         a.n_public = n_public;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch, nullptr,
-                        nullptr, cc);
+                        nullptr, cc, os.get());
+        os.done(true);
         copy_out(p, out);
         if (alpha_out) *alpha_out = p.alpha.abi();
         if (zeta_out) *zeta_out = p.zeta.abi();
@@ -318,8 +380,10 @@ int eon_prove_air_pp(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
         a.prog = prog;
         a.publics = publics;
         a.n_public = n_public;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
-                        pp ? pp->pp.get() : nullptr, nullptr, cc);
+                        pp ? pp->pp.get() : nullptr, nullptr, cc, os.get());
+        os.done(false);
         copy_out_pp(p, out);
     });
 }
@@ -337,8 +401,10 @@ int eon_prove_air_pp_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
         a.prog = prog;
         a.publics = publics;
         a.n_public = n_public;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch,
-                        pp ? pp->pp.get() : nullptr, nullptr, cc);
+                        pp ? pp->pp.get() : nullptr, nullptr, cc, os.get());
+        os.done(true);
         copy_out_pp(p, out);
         if (alpha_out) *alpha_out = p.alpha.abi();
         if (zeta_out) *zeta_out = p.zeta.abi();
@@ -365,8 +431,10 @@ int eon_prove_air_lk(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
         LookupInputs lk;
         lk.pre_trace = pre_trace;
         lk.challenges = challenges;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, nullptr, nullptr,
-                        pp ? pp->pp.get() : nullptr, &lk, cc);
+                        pp ? pp->pp.get() : nullptr, &lk, cc, os.get());
+        os.done(false);
         copy_out_lk(p, out);
     });
 }
@@ -386,8 +454,10 @@ int eon_prove_air_lk_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon
         a.n_public = n_public;
         LookupInputs lk;
         lk.pre_trace = pre_trace;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, nullptr, &challenger->ch,
-                        pp ? pp->pp.get() : nullptr, &lk, cc);
+                        pp ? pp->pp.get() : nullptr, &lk, cc, os.get());
+        os.done(true);
         copy_out_lk(p, out);
         if (challenges_out)
             for (size_t i = 0; i < p.perm_challenges.size(); i++) challenges_out[i] = p.perm_challenges[i].abi();
@@ -407,8 +477,10 @@ int eon_prove_p2air_fs(eon_kzg_pcs* pcs, const eon_p2air* air, const eon_fr* tra
         using namespace eon_host;
         AirRef a;
         a.p2 = air;
+        OpeningScope os(pcs);
         Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), max_constraint_degree, shard,
-                        &challenger->ch);
+                        &challenger->ch, nullptr, nullptr, nullptr, os.get());
+        os.done(true);
         copy_out(p, out);
         if (alpha_out) *alpha_out = p.alpha.abi();
         if (zeta_out) *zeta_out = p.zeta.abi();
@@ -437,7 +509,18 @@ int eon_verify_air(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proo
         in.n_challenges = n_challenges;
         in.alpha = Fr::from_abi(*alpha);
         in.zeta = Fr::from_abi(*zeta);
+        in.batched = pcs->opening == EON_OPENING_BATCHED;
+        if (in.batched && (!pcs->have_gamma || !pcs->have_delta))
+            throw Error(EON_E_ARG, "the batched opening without a challenger needs gamma and delta "
+                                   "(eon_kzg_pcs_set_opening_challenges)");
+        in.gamma = pcs->gamma;
+        in.delta = pcs->delta;
         const VerifyOutcome o = verify(*pcs->pcs, in, nullptr);
+        if (in.batched) {
+            pcs->have_last = true;
+            pcs->last_gamma = o.gamma;
+            pcs->last_delta = o.delta;
+        }
         *result = o.verdict;
         detail = o.detail;
     });
@@ -461,7 +544,13 @@ int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_p
         in.vk_width = vk_width;
         in.vk_degree_bits = vk_degree_bits;
         in.vk_commitment = vk_commitment;
+        in.batched = pcs->opening == EON_OPENING_BATCHED;
         const VerifyOutcome o = verify(*pcs->pcs, in, &challenger->ch);
+        if (in.batched) {
+            pcs->have_last = true;
+            pcs->last_gamma = o.gamma;
+            pcs->last_delta = o.delta;
+        }
         *result = o.verdict;
         detail = o.detail;
         if (o.verdict == EON_VERIFY_INVALID_PROOF_SHAPE) return;  // rejected before the transcript
@@ -479,11 +568,12 @@ int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_p
 namespace {
 
 void copy_out(const eon_host::Proof& p, eon_proof* out) {
-    const size_t w = p.trace_commit.size(), c = p.quotient_commit.size();
+    // nw: the witnesses per point, w per column or one in the batched mode ([2] compact entries)
+    const size_t w = p.trace_commit.size(), c = p.quotient_commit.size(), nw = p.trace_witnesses[0].size();
     std::memcpy(out->trace_commit, p.trace_commit.data(), w * sizeof(eon_g1_affine));
     for (int k = 0; k < 2; k++) {
         std::memcpy(out->trace_opened + k * w, p.trace_opened[k].data(), w * sizeof(eon_fr));
-        std::memcpy(out->trace_witnesses + k * w, p.trace_witnesses[k].data(), w * sizeof(eon_g1_affine));
+        std::memcpy(out->trace_witnesses + k * nw, p.trace_witnesses[k].data(), nw * sizeof(eon_g1_affine));
     }
     std::memcpy(out->quotient_commit, p.quotient_commit.data(), c * sizeof(eon_g1_affine));
     std::memcpy(out->quotient_opened, p.quotient_opened.data(), c * sizeof(eon_fr));
@@ -494,23 +584,23 @@ void copy_out(const eon_host::Proof& p, eon_proof* out) {
 
 void copy_out_pp(const eon_host::Proof& p, eon_proof_pp* out) {
     copy_out(p, &out->base);
-    const size_t w = p.pre_commit.size();
+    const size_t w = p.pre_commit.size(), nw = p.pre_witnesses[0].size();
     if (!w) return;
     std::memcpy(out->preprocessed_commit, p.pre_commit.data(), w * sizeof(eon_g1_affine));
     for (int k = 0; k < 2; k++) {
         std::memcpy(out->preprocessed_opened + k * w, p.pre_opened[k].data(), w * sizeof(eon_fr));
-        std::memcpy(out->preprocessed_witnesses + k * w, p.pre_witnesses[k].data(), w * sizeof(eon_g1_affine));
+        std::memcpy(out->preprocessed_witnesses + k * nw, p.pre_witnesses[k].data(), nw * sizeof(eon_g1_affine));
     }
 }
 
 void copy_out_lk(const eon_host::Proof& p, eon_proof_lk* out) {
     copy_out_pp(p, &out->pp);
-    const size_t w = p.perm_commit.size();
+    const size_t w = p.perm_commit.size(), nw = p.perm_witnesses[0].size();
     if (!w) return;
     std::memcpy(out->permutation_commit, p.perm_commit.data(), w * sizeof(eon_g1_affine));
     for (int k = 0; k < 2; k++) {
         std::memcpy(out->permutation_opened + k * w, p.perm_opened[k].data(), w * sizeof(eon_fr));
-        std::memcpy(out->permutation_witnesses + k * w, p.perm_witnesses[k].data(), w * sizeof(eon_g1_affine));
+        std::memcpy(out->permutation_witnesses + k * nw, p.perm_witnesses[k].data(), nw * sizeof(eon_g1_affine));
     }
 }
 

@@ -438,4 +438,97 @@ std::vector<Opened> KzgPcs::open(const std::vector<OpenRound>& rounds) {
     return out;
 }
 
+std::vector<Opened> KzgPcs::open_values(const std::vector<OpenRound>& rounds) {
+    require_prover("open");
+    for (const OpenRound& r : rounds)
+        if (r.data->size() != r.points.size()) throw Error(EON_E_SHAPE, "one point list per matrix");
+    hipStream_t st = static_cast<hipStream_t>(eon_ctx_stream(ctx_));
+    struct DrainOnExit {  // an error path must not free the buffers under the kernels writing them
+        hipStream_t s;
+        ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+    } drain{st};
+    std::vector<Opened> out(rounds.size());
+    std::vector<std::vector<DeviceBuffer>> vals(rounds.size());
+    for (size_t r = 0; r < rounds.size(); r++) {
+        const auto& data = *rounds[r].data;
+        out[r].values.resize(data.size());
+        out[r].witnesses.resize(data.size());
+        for (size_t m = 0; m < data.size(); m++) {
+            const MatrixProverData& md = data[m];
+            const std::vector<Fr>& pts = rounds[r].points[m];
+            const uint32_t w = md.coeffs.width;
+            vals[r].emplace_back(std::max<uint64_t>(pts.size() * w, 1) * sizeof(eon_fr));
+            std::vector<eon_fr> zs(pts.size());
+            for (size_t p = 0; p < pts.size(); p++) zs[p] = pts[p].abi();
+            check(ctx_,
+                  eon_eval_columns_dev(ctx_, md.coeffs.data(), md.coeffs.height, w, zs.data(), (uint32_t)zs.size(),
+                                       vals[r].back().as<eon_fr>()),
+                  "opened values");
+        }
+    }
+    for (size_t r = 0; r < rounds.size(); r++)
+        for (size_t m = 0; m < rounds[r].data->size(); m++) {
+            const size_t np = rounds[r].points[m].size();
+            const uint32_t w = (*rounds[r].data)[m].coeffs.width;
+            std::vector<eon_fr> hv(np * w);
+            hip_check(hipMemcpyAsync(hv.data(), vals[r][m].get(), hv.size() * sizeof(eon_fr), hipMemcpyDeviceToHost,
+                                     st),
+                      "opened values");
+            hip_check(hipStreamSynchronize(st), "opened values");
+            out[r].values[m].resize(np);
+            out[r].witnesses[m].resize(np);
+            for (size_t p = 0; p < np; p++) out[r].values[m][p].assign(hv.begin() + p * w, hv.begin() + (p + 1) * w);
+        }
+    return out;
+}
+
+std::vector<Opened> KzgPcs::open_batched(const std::vector<OpenRound>& rounds, const Fr& gamma,
+                                         std::vector<Opened>* values) {
+    require_prover("open");
+    std::vector<Opened> out = values ? std::move(*values) : open_values(rounds);
+    if (out.size() != rounds.size()) throw Error(EON_E_SHAPE, "opened values of other rounds");
+    hipStream_t st = static_cast<hipStream_t>(eon_ctx_stream(ctx_));
+    struct DrainOnExit {
+        hipStream_t s;
+        ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+    } drain{st};
+    const eon_fr g = gamma.abi();
+    for (size_t r = 0; r < rounds.size(); r++) {
+        const auto& data = *rounds[r].data;
+        if (data.size() != rounds[r].points.size() || out[r].values.size() != data.size())
+            throw Error(EON_E_SHAPE, "one point list per matrix");
+        out[r].witnesses.resize(data.size());
+        for (size_t m = 0; m < data.size(); m++) {
+            const MatrixProverData& md = data[m];
+            const std::vector<Fr>& pts = rounds[r].points[m];
+            const uint64_t h = md.coeffs.height;
+            const uint32_t w = md.coeffs.width, np = (uint32_t)pts.size();
+            // a constant (or empty) folded polynomial has the empty quotient: the identity
+            out[r].witnesses[m].assign(np, std::vector<eon_g1_affine>(1, eon_g1_affine{}));
+            if (np == 0 || h < 2 || w == 0) continue;
+            // F = sum_j gamma^j f_j; a single column is its own fold
+            DeviceBuffer folded;
+            const eon_fr* f = md.coeffs.data();
+            if (w > 1) {
+                folded = DeviceBuffer(h * sizeof(eon_fr));
+                check(ctx_, eon_fr_fold_columns_dev(ctx_, md.coeffs.data(), h, w, &g, nullptr, folded.as<eon_fr>()),
+                      "fold columns");
+                f = folded.as<eon_fr>();
+            }
+            DeviceBuffer quot((h - 1) * np * sizeof(eon_fr)), fz(np * sizeof(eon_fr));
+            std::vector<eon_fr> zs(np);
+            for (uint32_t p = 0; p < np; p++) zs[p] = pts[p].abi();
+            check(ctx_,
+                  eon_quotient_and_eval_columns_multi_dev(ctx_, f, h, 1, zs.data(), np, quot.as<eon_fr>(),
+                                                          fz.as<eon_fr>()),
+                  "folded quotients");
+            std::vector<eon_g1_affine> wits(np);
+            check(ctx_, eon_msm_g1_columns_dev(ctx_, bases_, quot.as<eon_fr>(), h - 1, np, wits.data()),
+                  "batched witnesses");
+            for (uint32_t p = 0; p < np; p++) out[r].witnesses[m][p][0] = wits[p];
+        }
+    }
+    return out;
+}
+
 }  // namespace eon_host

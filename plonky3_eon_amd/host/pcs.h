@@ -149,6 +149,19 @@ class KzgPcs {
     // (eon_kzg_opening_bases_create), reusing the digits sorted at commit time, so every matrix
     // must come from commit / commit_columns (which keep those digits); otherwise EON_E_ARG.
     std::vector<Opened> open(const std::vector<OpenRound>& rounds);
+    // The opened values of `open` alone (eon_eval_columns_dev per matrix), witnesses left empty: what
+    // the batched mode's transcript observes before gamma exists.
+    std::vector<Opened> open_values(const std::vector<OpenRound>& rounds);
+    // The batched opening: the same opened values as `open`, and ONE witness per (matrix, point),
+    // witnesses[m][p] = { commit_column(quotient_and_eval(F, z_p).0) } with F = sum_j gamma^j f_j
+    // folded once per matrix from its coefficients (eon_fr_fold_columns_dev), the quotients of all of
+    // a matrix's points from one eon_quotient_and_eval_columns_multi_dev at width 1 and their MSMs
+    // from one eon_msm_g1_columns_dev over the SRS bases.  A width-1 matrix is its own fold, so its
+    // witness is bit for bit `open`'s.  `values` (optional): the result of open_values(rounds), when
+    // the caller needed it first to derive gamma; it is moved into the result instead of recomputed.
+    // This is NOT the reference's KzgProof: see INTEGRATION.md, BatchedKzgPcs.
+    std::vector<Opened> open_batched(const std::vector<OpenRound>& rounds, const Fr& gamma,
+                                     std::vector<Opened>* values = nullptr);
     // init_srs_unsafe's g2_alpha = [alpha] G2 (params.rs:123-139), the verifier's half of the SRS:
     // made by eon_g2_mul at the first verify and kept; a supplied SRS's own otherwise
     const eon_g2_affine& g2_alpha();

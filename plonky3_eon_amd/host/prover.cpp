@@ -87,8 +87,13 @@ std::unique_ptr<Preprocessed> setup_preprocessed(KzgPcs& pcs, const eon_fr* pre_
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha_in,
             const Fr& zeta_in, uint32_t max_constraint_degree, const eon_collective* shard,
             DuplexChallenger* challenger, const Preprocessed* pp, const LookupInputs* lookups,
-            ConstraintCheck* constraint_check) {
+            ConstraintCheck* constraint_check, BatchedOpening* batched) {
     pcs.require_prover("prove");
+    if (batched && shard && shard->world > 1)
+        throw Error(EON_E_ARG, "the batched opening is not lane-sharded: prove on one device or per column");
+    if (batched && !challenger && !batched->have_gamma)
+        throw Error(EON_E_ARG, "the batched opening without a challenger needs gamma "
+                               "(eon_kzg_pcs_set_opening_challenges)");
     eon_ctx* ctx = pcs.ctx();
     using clock = std::chrono::steady_clock;
     auto tick = [&] {
@@ -362,7 +367,26 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         ~CollectiveScope() { (void)eon_ctx_set_collective(c, nullptr); }
     };
     std::vector<Opened> opened;
-    {
+    if (batched) {
+        // gamma follows the opened values, delta the witnesses (prover.h, BatchedOpening)
+        Fr gamma = batched->gamma;
+        if (challenger) {
+            opened = pcs.open_values(rounds);
+            for (const Opened& o : opened)
+                for (const auto& mat : o.values)
+                    for (const auto& at_point : mat)
+                        for (const eon_fr& v : at_point) challenger->observe(Fr::from_abi(v));
+            gamma = challenger->sample();
+        }
+        opened = pcs.open_batched(rounds, gamma, challenger ? &opened : nullptr);
+        batched->gamma_used = gamma;
+        if (challenger) {
+            for (const Opened& o : opened)
+                for (const auto& mat : o.witnesses)
+                    for (const auto& at_point : mat) challenger->observe_g1(at_point.data(), at_point.size());
+            batched->delta_used = challenger->sample();
+        }
+    } else {
         CollectiveScope scope(ctx, shard);
         opened = pcs.open(rounds);  // prover.rs:424-442
     }

@@ -68,6 +68,20 @@ struct ConstraintCheck {
     eon_constraint_report report{};
 };
 
+// The batched opening mode (EON_OPENING_BATCHED): when a prove is given one, the open stage is
+// KzgPcs::open_batched -- one witness per (matrix, point), every witness vector of the Proof then
+// has ONE entry per point -- and no lane sharding (EON_E_ARG).  Claims are numbered in the round
+// order: trace zeta, trace zeta h; [permutation zeta, zeta h]; chunk 0..C-1 at zeta; [preprocessed
+// zeta, zeta h].  With a challenger the transcript goes on after zeta: every opened value in claim
+// order, column by column; gamma sampled; the K witnesses in claim order (observe_g1); delta
+// sampled -- the verifier does the same, so both challengers end in the same state.  Without one,
+// `gamma` is an input (have_gamma; missing is EON_E_ARG) and delta is the verifier's alone.
+struct BatchedOpening {
+    bool have_gamma = false;
+    Fr gamma = Fr::zero();
+    Fr gamma_used = Fr::zero(), delta_used = Fr::zero();  // out; delta only with a challenger
+};
+
 // The AIR being proved: the fused Poseidon2-AIR kernel (lane-shardable), or a generic constraint
 // program compiled from get_symbolic_constraints (eon_air_program) with its public values.
 struct AirRef {
@@ -91,9 +105,12 @@ struct AirRef {
 // alpha (:300), extended next to the trace (:317-319) and opened at {zeta, zeta h} in the round
 // after the trace's (:427-437).  `check` (programs only; null = off, the prove is then launch for
 // launch what it is without it): see ConstraintCheck; its time is counted in EON_STAGE_TRACE_LDE.
+// `batched` (null = the per-column opening, byte for byte and launch for launch what it is without
+// it): see BatchedOpening.
 Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height, const Fr& alpha,
             const Fr& zeta, uint32_t max_constraint_degree, const eon_collective* shard,
             DuplexChallenger* challenger = nullptr, const Preprocessed* preprocessed = nullptr,
-            const LookupInputs* lookups = nullptr, ConstraintCheck* check = nullptr);
+            const LookupInputs* lookups = nullptr, ConstraintCheck* check = nullptr,
+            BatchedOpening* batched = nullptr);
 
 }  // namespace eon_host

@@ -11,6 +11,91 @@ namespace eon_host {
 
 namespace {
 
+// A G1 point as the reference's deserialisation admits it: the identity (0, 0), or canonical
+// coordinates with y^2 = x^3 + 3 (Montgomery residues; G1 has cofactor 1, so on the curve is in the
+// group).  The batched verify folds commitments through an MSM before the pairing check sees them,
+// so the raw points are tested here.
+struct Fq4 {
+    uint64_t l[4];
+};
+constexpr uint64_t FQ_P[4] = {0x3c208c16d87cfd47ull, 0x97816a916871ca8dull, 0xb85045b68181585dull,
+                              0x30644e72e131a029ull};
+// 3 * 2^256 mod q: the curve's b in Montgomery form
+constexpr uint64_t FQ_THREE[4] = {0x7a17caa950ad28d7ull, 0x1f6ac17ae15521b9ull, 0x334bea4e696bd284ull,
+                                  0x2a1f6744ce179d8eull};
+
+bool fq_geq_p(const Fq4& a) {
+    for (int i = 3; i >= 0; i--)
+        if (a.l[i] != FQ_P[i]) return a.l[i] > FQ_P[i];
+    return true;
+}
+
+// a b 2^-256 mod q, canonical (CIOS; a, b < q)
+Fq4 fq_mul(const Fq4& a, const Fq4& b) {
+    typedef unsigned __int128 u128;
+    uint64_t inv = 1;  // -q^-1 mod 2^64 by Newton iteration
+    for (int i = 0; i < 6; i++) inv *= 2 - FQ_P[0] * inv;
+    inv = ~inv + 1;
+    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) {
+        u128 c = 0;
+        for (int j = 0; j < 4; j++) {
+            c += (u128)a.l[j] * b.l[i] + t[j];
+            t[j] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[4] = (uint64_t)c;
+        t[5] = (uint64_t)(c >> 64);
+        const uint64_t m = t[0] * inv;
+        c = (u128)m * FQ_P[0] + t[0];
+        c >>= 64;
+        for (int j = 1; j < 4; j++) {
+            c += (u128)m * FQ_P[j] + t[j];
+            t[j - 1] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[3] = (uint64_t)c;
+        t[4] = t[5] + (uint64_t)(c >> 64);
+    }
+    Fq4 r{{t[0], t[1], t[2], t[3]}};
+    if (t[4] || fq_geq_p(r)) {
+        uint64_t borrow = 0;
+        for (int i = 0; i < 4; i++) {
+            const u128 x = (u128)r.l[i] - FQ_P[i] - borrow;
+            r.l[i] = (uint64_t)x;
+            borrow = (uint64_t)(x >> 64) & 1;
+        }
+    }
+    return r;
+}
+
+bool g1_valid(const eon_g1_affine& p) {
+    typedef unsigned __int128 u128;
+    Fq4 x, y;
+    for (int i = 0; i < 4; i++) x.l[i] = p.x[i], y.l[i] = p.y[i];
+    if (!(x.l[0] | x.l[1] | x.l[2] | x.l[3] | y.l[0] | y.l[1] | y.l[2] | y.l[3])) return true;
+    if (fq_geq_p(x) || fq_geq_p(y)) return false;
+    Fq4 rhs = fq_mul(fq_mul(x, x), x);
+    u128 c = 0;
+    for (int i = 0; i < 4; i++) {  // + 3: below 2q < 2^255
+        c += (u128)rhs.l[i] + FQ_THREE[i];
+        rhs.l[i] = (uint64_t)c;
+        c >>= 64;
+    }
+    if (fq_geq_p(rhs)) {
+        uint64_t borrow = 0;
+        for (int i = 0; i < 4; i++) {
+            const u128 d = (u128)rhs.l[i] - FQ_P[i] - borrow;
+            rhs.l[i] = (uint64_t)d;
+            borrow = (uint64_t)(d >> 64) & 1;
+        }
+    }
+    const Fq4 lhs = fq_mul(y, y);
+    return lhs.l[0] == rhs.l[0] && lhs.l[1] == rhs.l[1] && lhs.l[2] == rhs.l[2] && lhs.l[3] == rhs.l[3];
+}
+
 VerifyOutcome verdict(VerifyOutcome o, int v, const std::string& why) {
     o.verdict = v;
     o.detail = why;
@@ -125,7 +210,111 @@ VerifyOutcome verify(KzgPcs& pcs, const VerifyInputs& in, DuplexChallenger* chal
         if (e.code != EON_E_DEGREE_TOO_LARGE) throw;
         return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT, std::string("KzgError::DegreeTooLarge: ") + e.what());
     }
-    {
+    if (in.batched) {
+        // The batched opening (EON_OPENING_BATCHED; not the reference's proof format): claim i =
+        // (matrix, point) in the round order carries ONE witness W_i.  With C_i = sum_j gamma^j C_(m,j)
+        // and v_i = sum_j gamma^j v_(i,j), the K claims go to ONE eon_kzg_verify_batch as
+        // (delta^i C_i, delta^i W_i, delta^i v_i, z_i): prod_i e(delta^i (C_i - v_i G1), G2)
+        // e(-delta^i W_i, g2_alpha - z_i G2) = 1.  The weights are what makes the product a sound
+        // batch check (the per-column mode keeps the reference's unweighted one).
+        struct Claim {
+            const eon_g1_affine* commit;
+            const eon_fr* values;
+            const eon_g1_affine* witness;
+            uint32_t w;
+            Fr z;
+        };
+        std::vector<Claim> claims;
+        auto matrix = [&](const eon_g1_affine* commit, const eon_fr* opened, const eon_g1_affine* wit, uint32_t w) {
+            claims.push_back({commit, opened, wit, w, zeta});
+            claims.push_back({commit, opened + w, wit + 1, w, zeta_next});
+        };
+        matrix(b.trace_commit, b.trace_opened, b.trace_witnesses, width);
+        if (has_perm_commit) matrix(lk.permutation_commit, lk.permutation_opened, lk.permutation_witnesses, perm_width);
+        for (uint32_t c = 0; c < num_chunks; c++)
+            claims.push_back({b.quotient_commit + c, b.quotient_opened + c, b.quotient_witnesses + c, 1, zeta});
+        if (pre_width > 0) matrix(in.vk_commitment, pp.preprocessed_opened, pp.preprocessed_witnesses, pre_width);
+        // what the reference's deserialisation would refuse is no opening (as in the per-column mode)
+        for (const Claim& c : claims) {
+            for (uint32_t j = 0; j < c.w; j++)
+                if (!fr_is_canonical(Fr::from_abi(c.values[j])))
+                    return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
+                                   "malformed opening: an opened value is not a canonical Fr");
+            for (uint32_t j = 0; j < c.w; j++)
+                if (!g1_valid(c.commit[j]))
+                    return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
+                                   "malformed opening: a commitment is not a point of G1");
+            if (!g1_valid(*c.witness))
+                return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
+                               "malformed opening: a witness is not a point of G1");
+        }
+        out.gamma = in.gamma;
+        out.delta = in.delta;
+        if (challenger) {
+            for (const Claim& c : claims)
+                for (uint32_t j = 0; j < c.w; j++) challenger->observe(Fr::from_abi(c.values[j]));
+            out.gamma = challenger->sample();
+            for (const Claim& c : claims) challenger->observe_g1(c.witness, 1);
+            out.delta = challenger->sample();
+        } else if (!fr_is_canonical(out.gamma) || !fr_is_canonical(out.delta)) {
+            throw Error(EON_E_ARG, "gamma or delta is not a canonical Fr");
+        }
+        // Every scaled point from ONE variable-base column MSM: the bases are the proof's commitments
+        // (a matrix's once, shared by its two claims) followed by the K witnesses; column i of the
+        // scalar matrix holds delta^i gamma^j on the rows of claim i's commitments and gives
+        // delta^i C_i, column K + i holds delta^i on the row of W_i and gives delta^i W_i.
+        const size_t K = claims.size();
+        std::vector<eon_g1_affine> pts;
+        std::vector<size_t> first(K);
+        for (size_t i = 0; i < K; i++) {
+            if (i > 0 && claims[i].commit == claims[i - 1].commit) {
+                first[i] = first[i - 1];
+                continue;
+            }
+            first[i] = pts.size();
+            pts.insert(pts.end(), claims[i].commit, claims[i].commit + claims[i].w);
+        }
+        const size_t wit0 = pts.size();
+        for (const Claim& c : claims) pts.push_back(*c.witness);
+        const size_t n_pts = pts.size(), cols = 2 * K;
+        std::vector<eon_fr> scal(n_pts * cols, eon_fr{{0, 0, 0, 0}});
+        std::vector<eon_fr> vs(K), zs(K);
+        Fr dpow = Fr::one();
+        for (size_t i = 0; i < K; i++) {
+            const Claim& c = claims[i];
+            Fr s = dpow, v = Fr::zero();
+            for (uint32_t j = 0; j < c.w; j++) {
+                scal[(first[i] + j) * cols + i] = s.abi();
+                v = fr_sum(v, fr_mul(s, Fr::from_abi(c.values[j])));
+                s = fr_mul(s, out.gamma);
+            }
+            scal[(wit0 + i) * cols + K + i] = dpow.abi();
+            vs[i] = v.abi();
+            zs[i] = c.z.abi();
+            dpow = fr_mul(dpow, out.delta);
+        }
+        std::vector<eon_g1_affine> scaled(cols);
+        {
+            eon_msm_bases* bases = nullptr;
+            check(ctx, eon_msm_bases_create(ctx, pts.data(), n_pts, 0, &bases), "eon_msm_bases_create");
+            const int mrc = eon_msm_g1_columns(ctx, bases, scal.data(), n_pts, (uint32_t)cols, scaled.data());
+            eon_msm_bases_destroy(bases);
+            check(ctx, mrc, "eon_msm_g1_columns");
+        }
+        int ok = 0;
+        const int rc = eon_kzg_verify_batch(ctx, scaled.data(), scaled.data() + K, vs.data(), zs.data(), K,
+                                            &pcs.g2_alpha(), &ok);
+        if (rc == EON_E_ARG) {
+            const char* msg = eon_last_error(ctx);
+            return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
+                           std::string("malformed opening: ") + (msg ? msg : "invalid argument"));
+        }
+        check(ctx, rc, "eon_kzg_verify_batch");
+        if (!ok)
+            return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
+                           "KzgError::ProofShapeMismatch: the weighted pairing check of " + std::to_string(K) +
+                               " batched openings failed");
+    } else {
         // the reference's round order: trace at {zeta, zeta h}, permutation at {zeta, zeta h}, quotient
         // chunks at {zeta}, preprocessed at {zeta, zeta h} (:415-471)
         std::vector<eon_g1_affine> cs, ws;

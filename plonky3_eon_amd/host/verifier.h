@@ -27,6 +27,10 @@ struct VerifyInputs {
     const eon_fr* challenges = nullptr;
     uint32_t n_challenges = 0;
     Fr alpha = Fr::zero(), zeta = Fr::zero();
+    // EON_OPENING_BATCHED: the witness arrays of the proof hold ONE point per opened point ([2],
+    // [2], [C], [2]); without a challenger gamma and delta are the ones given here
+    bool batched = false;
+    Fr gamma = Fr::zero(), delta = Fr::zero();
 };
 
 struct VerifyOutcome {
@@ -34,6 +38,7 @@ struct VerifyOutcome {
     std::string detail;           // why, when not OK
     Fr alpha = Fr::zero(), zeta = Fr::zero();  // the challenges used (sampled with a challenger)
     std::vector<Fr> challenges;
+    Fr gamma = Fr::zero(), delta = Fr::zero();  // batched mode: the opening challenges used
 };
 
 // Throws Error for bad arguments and device errors (negative codes); every other outcome is a

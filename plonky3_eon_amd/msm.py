@@ -201,6 +201,27 @@ def srs_powers(n: int, alpha, ctx: Context | None = None) -> np.ndarray:
     return out
 
 
+def fold_columns(mat, gamma, scale=None, ctx: Context | None = None):
+    """out[i] = scale * sum_j gamma^j mat[i][j] of a device (rows, width, 4) Fr matrix -> a device
+    (rows, 4) tensor (eon_fr_fold_columns_dev): the folded polynomial of the batched KZG opening.
+    `gamma` / `scale` are ints or Fr limbs (fr_to_abi); scale None = one."""
+    import torch
+
+    from .field import fr_to_abi
+
+    ctx = ctx or default_context(0)
+    m = mat.contiguous()
+    rows, width = int(m.shape[0]), int(m.shape[1])
+    out = torch.empty((rows, 4), dtype=m.dtype, device=m.device)
+    g = fr_to_abi(gamma)
+    s = fr_to_abi(scale) if scale is not None else None
+    ctx.set_stream(torch.cuda.current_stream(m.device).cuda_stream)
+    ctx.check(ctx.lib.eon_fr_fold_columns_dev(ctx.handle, ctypes.c_void_p(m.data_ptr()), rows, width, ctypes.byref(g),
+                                              ctypes.byref(s) if s is not None else None,
+                                              ctypes.c_void_p(out.data_ptr())))
+    return out
+
+
 def multi_exp(points, scalars, ctx: Context | None = None) -> np.ndarray:
     """G1::multi_exp: panics (EonError) on a length mismatch, identity for empty input."""
     ctx = ctx or default_context(0)

@@ -36,6 +36,9 @@ STAGES = ["commit to trace data", "trace LDE (get_evaluations_on_domain)", "quot
           "exchange partial quotients", "commit to quotient poly chunks", "open", "assemble columns"]
 EON_STAGES = 8
 EON_SRS_TRUSTED = 1  # eon_kzg_pcs_create_from_srs flags: skip eon_kzg_srs_check
+EON_OPENING_PER_COLUMN = 0
+EON_OPENING_BATCHED = 1
+OPENING_MODES = {"per_column": EON_OPENING_PER_COLUMN, "batched": EON_OPENING_BATCHED}
 
 class eon_proof(ctypes.Structure):
     _fields_ = [("trace_commit", _P), ("quotient_commit", _P), ("trace_opened", _P), ("trace_witnesses", _P),
@@ -67,6 +70,10 @@ SIGNATURES = {
     "eon_kzg_pcs_set_check_constraints": (_INT, [_P, _INT]),
     "eon_kzg_pcs_check_constraints": (_INT, [_P]),
     "eon_kzg_pcs_last_constraint_report": (_INT, [_P, ctypes.POINTER(_lib.eon_constraint_report)]),
+    "eon_kzg_pcs_set_opening": (_INT, [_P, _U32]),
+    "eon_kzg_pcs_opening": (_INT, [_P]),
+    "eon_kzg_pcs_set_opening_challenges": (_INT, [_P, _P, _P]),
+    "eon_kzg_pcs_last_opening_challenges": (_INT, [_P, _P, _P]),
     "eon_rccl_unique_id": (_INT, [_P]),
     "eon_rccl_collective_init": (_INT, [_U32, _U32, _P, ctypes.POINTER(eon_collective)]),
     "eon_rccl_collective_info": (_INT, [ctypes.POINTER(eon_collective), ctypes.POINTER(ctypes.c_int32),
@@ -227,6 +234,43 @@ class NativeKzgPcs:
         _check(self.lib.eon_kzg_pcs_last_constraint_report(self._h, ctypes.byref(rep)),
                "eon_kzg_pcs_last_constraint_report")
         return ConstraintReport.from_abi(rep)
+
+    def opening_scope(self, opening: str, gamma=None, delta=None):
+        """Context manager: the pcs's opening mode ("per_column" / "batched") and fixed opening
+        challenges (canonical ints or None) for one call, the mode restored afterwards.  The
+        per-column mode makes no C call at all, so a default prove is what it is without this."""
+        import contextlib
+
+        if opening not in OPENING_MODES:
+            raise ValueError(f"opening must be one of {sorted(OPENING_MODES)}, not {opening!r}")
+
+        @contextlib.contextmanager
+        def scope():
+            if opening == "per_column":
+                if self.lib.eon_kzg_pcs_opening(self._h) == EON_OPENING_PER_COLUMN:
+                    yield
+                    return
+            before = self.lib.eon_kzg_pcs_opening(self._h)
+            g = fr_to_abi(gamma) if gamma is not None else None
+            d = fr_to_abi(delta) if delta is not None else None
+            _check(self.lib.eon_kzg_pcs_set_opening_challenges(self._h, ctypes.byref(g) if g is not None else None,
+                                                               ctypes.byref(d) if d is not None else None),
+                   "eon_kzg_pcs_set_opening_challenges")
+            _check(self.lib.eon_kzg_pcs_set_opening(self._h, OPENING_MODES[opening]), "eon_kzg_pcs_set_opening")
+            try:
+                yield
+            finally:
+                self.lib.eon_kzg_pcs_set_opening(self._h, before)
+
+        return scope()
+
+    def last_opening_challenges(self):
+        """(gamma, delta) of the last batched prove or verify on this pcs, canonical ints."""
+        g, d = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+        _check(self.lib.eon_kzg_pcs_last_opening_challenges(self._h, _p(g), _p(d)),
+               "eon_kzg_pcs_last_opening_challenges")
+        unm = lambda v: fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v)))  # noqa: E731
+        return unm(g), unm(d)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -479,10 +523,17 @@ def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: 
             raise bad_shape(f"{what}: one matrix opened at two points expected")
         v = [mat(x, 4) for x in op.values[0]]
         w = [mat(x, 8) for x in op.witnesses[0]]
-        if any(x.shape[0] != width for x in v + w):
-            raise bad_shape(f"{what}: opened widths {[x.shape[0] for x in v + w]}, expected {width}")
+        if any(x.shape[0] != width for x in v):
+            raise bad_shape(f"{what}: opened widths {[x.shape[0] for x in v]}, expected {width}")
+        nw = 1 if batched else width  # one witness per point in the batched mode
+        if any(x.shape[0] != nw for x in w):
+            raise bad_shape(f"{what}: {[x.shape[0] for x in w]} witnesses per point, the {opening} opening has {nw}")
         return np.ascontiguousarray(np.stack(v)), np.ascontiguousarray(np.stack(w))
 
+    opening = getattr(proof, "opening", "per_column")
+    if opening not in OPENING_MODES:
+        raise bad_shape(f"unknown opening mode {opening!r}")
+    batched = opening == "batched"
     has_perm = proof.permutation_commit is not None
     opened = list(proof.opened)
     if len(opened) < 2 + (1 if has_perm else 0) or len(opened) > 3 + (1 if has_perm else 0):
@@ -540,17 +591,22 @@ def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: 
             raise bad_shape(f"{len(chal)} permutation challenges, the AIR has {prog.num_challenges}")
         ch = _publics_limbs(chal)
         a, z = fr_to_abi(proof.alpha), fr_to_abi(proof.zeta)
-        pcs.check(pcs.lib.eon_verify_air(pcs._h, prog.handle, ctypes.byref(out_lk), _p(pub), npub, vk_w, vk_bits, vkp,
-                                         _p(ch), len(chal), ctypes.byref(a), ctypes.byref(z), ctypes.byref(res)))
+        with pcs.opening_scope(opening, proof.gamma if batched else None, proof.delta if batched else None):
+            pcs.check(pcs.lib.eon_verify_air(pcs._h, prog.handle, ctypes.byref(out_lk), _p(pub), npub, vk_w, vk_bits,
+                                             vkp, _p(ch), len(chal), ctypes.byref(a), ctypes.byref(z),
+                                             ctypes.byref(res)))
         used = {"alpha": proof.alpha, "zeta": proof.zeta, "permutation_challenges": chal}
     else:
         a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
         c_out = np.zeros((max(1, prog.num_challenges), 4), np.uint64)
-        pcs.check(pcs.lib.eon_verify_air_fs(pcs._h, prog.handle, ctypes.byref(out_lk), _p(pub), npub, vk_w, vk_bits,
-                                            vkp, challenger.handle, ctypes.byref(res), _p(c_out), _p(a_out),
-                                            _p(z_out)))
+        with pcs.opening_scope(opening):
+            pcs.check(pcs.lib.eon_verify_air_fs(pcs._h, prog.handle, ctypes.byref(out_lk), _p(pub), npub, vk_w,
+                                                vk_bits, vkp, challenger.handle, ctypes.byref(res), _p(c_out),
+                                                _p(a_out), _p(z_out)))
         used = {"alpha": unm(a_out), "zeta": unm(z_out),
                 "permutation_challenges": [unm(c) for c in c_out[:prog.num_challenges]] if has_perm else []}
+    if batched and res.value != 1:
+        used["gamma"], used["delta"] = pcs.last_opening_challenges()
     if transcript is not None and res.value != 1:  # a shape rejection comes before the transcript
         transcript.update(used)
     if res.value != 0:
@@ -561,7 +617,8 @@ def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: 
 def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | None,
                  max_constraint_degree: int = 3, collective=None, challenger: Challenger | None = None,
                  public_values=(), preprocessed: Preprocessed | None = None, permutation_challenges=None,
-                 preprocessed_trace=None) -> Proof:
+                 preprocessed_trace=None, opening: str = "per_column", gamma: int | None = None,
+                 delta: int | None = None) -> Proof:
     """prover.prove through the C++ driver.  `air` is a Poseidon2Air (fused quotient kernel) or an
     air.AirProgram (any AIR, with `public_values`: canonical ints).  `trace`: (N, width, 4) device
     tensor; with a collective (world > 1, Poseidon2 only) `air`/`trace` are this rank's lanes and
@@ -573,8 +630,21 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     ints) are given next to alpha and zeta, or sampled with `challenger`; `preprocessed_trace` is
     the (N, Wp, 4) preprocessed trace itself when a lookup reads it.  The proof then carries
     permutation_commit and permutation_challenges, and its `opened` list has the permutation
-    columns second (the reference's rounds: trace, permutation, quotient chunks, preprocessed)."""
+    columns second (the reference's rounds: trace, permutation, quotient chunks, preprocessed).
+
+    `opening` = "batched" (eon_kzg_pcs_set_opening, set for this call and restored) makes the
+    standard batched KZG opening instead of the reference's per-column one: commitments and opened
+    values are the same, every opened[r].witnesses[m][t] is ONE point, shape (1, 8).  Without a
+    challenger `gamma` is required (EonError EON_E_ARG otherwise; `delta` is the verifier's and is
+    carried in the Proof when given); with one both are sampled after zeta and returned in
+    proof.gamma / proof.delta.  No collective (ValueError)."""
     from .air import AirProgram, _publics_limbs
+
+    if opening not in OPENING_MODES:
+        raise ValueError(f"opening must be one of {sorted(OPENING_MODES)}, not {opening!r}")
+    batched = opening == "batched"
+    if batched and collective is not None and collective.c.world > 1:
+        raise ValueError("the batched opening is not lane-sharded: prove without a collective")
 
     generic = isinstance(air, AirProgram)
     world = collective.c.world if collective is not None else 1
@@ -584,7 +654,7 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     tc = np.zeros((w, 8), np.uint64)
     qc = np.zeros((chunks, 8), np.uint64)
     to = np.zeros((2, w, 4), np.uint64)
-    tw = np.zeros((2, w, 8), np.uint64)
+    tw = np.zeros((2, 1 if batched else w, 8), np.uint64)
     qo = np.zeros((chunks, 4), np.uint64)
     qw = np.zeros((chunks, 8), np.uint64)
     out = eon_proof(_p(tc), _p(qc), _p(to), _p(tw), _p(qo), _p(qw), 0)
@@ -594,7 +664,7 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         wp = preprocessed.width
         pc = np.zeros((wp, 8), np.uint64)
         po = np.zeros((2, wp, 4), np.uint64)
-        pw = np.zeros((2, wp, 8), np.uint64)
+        pw = np.zeros((2, 1 if batched else wp, 8), np.uint64)
         out_pp = eon_proof_pp(out, _p(pc), _p(po), _p(pw))
         out = out_pp.base  # a view: the driver's degree_bits and stage_ms land here
     lookups = generic and air.permutation_width > 0
@@ -604,7 +674,7 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         wq = air.permutation_width
         mc = np.zeros((wq, 8), np.uint64)
         mo = np.zeros((2, wq, 4), np.uint64)
-        mw = np.zeros((2, wq, 8), np.uint64)
+        mw = np.zeros((2, 1 if batched else wq, 8), np.uint64)
         if preprocessed is None:
             out_pp = eon_proof_pp(out, None, None, None)
         out_lk = eon_proof_lk(out_pp, _p(mc), _p(mo), _p(mw))
@@ -622,54 +692,55 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     if not generic and npub:
         raise ValueError("the Poseidon2-AIR has no public values")
     tp = ctypes.c_void_p(t.data_ptr())
-    if lookups:
-        pt = preprocessed_trace.contiguous() if preprocessed_trace is not None else None
-        ptp = ctypes.c_void_p(pt.data_ptr()) if pt is not None else None
-        pph = preprocessed.handle if preprocessed is not None else None
-        if challenger is None:
+    with pcs.opening_scope(opening, gamma, delta):
+        if lookups:
+            pt = preprocessed_trace.contiguous() if preprocessed_trace is not None else None
+            ptp = ctypes.c_void_p(pt.data_ptr()) if pt is not None else None
+            pph = preprocessed.handle if preprocessed is not None else None
+            if challenger is None:
+                a, z = fr_to_abi(alpha), fr_to_abi(zeta)
+                chal = [int(c) for c in (permutation_challenges or ())]
+                ch = _publics_limbs(chal)
+                pcs.check(pcs.lib.eon_prove_air_lk(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, pph, ptp,
+                                                   _p(ch), len(chal), ctypes.byref(a), ctypes.byref(z),
+                                                   ctypes.byref(out_lk)))
+            else:
+                a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+                c_out = np.zeros((air.num_challenges, 4), np.uint64)
+                pcs.check(pcs.lib.eon_prove_air_lk_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, pph, ptp,
+                                                      challenger.handle, ctypes.byref(out_lk), _p(c_out), _p(a_out),
+                                                      _p(z_out)))
+                unm = lambda v: fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v)))  # noqa: E731
+                alpha, zeta, chal = unm(a_out), unm(z_out), [unm(c) for c in c_out]
+        elif challenger is None:
             a, z = fr_to_abi(alpha), fr_to_abi(zeta)
-            chal = [int(c) for c in (permutation_challenges or ())]
-            ch = _publics_limbs(chal)
-            pcs.check(pcs.lib.eon_prove_air_lk(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, pph, ptp,
-                                               _p(ch), len(chal), ctypes.byref(a), ctypes.byref(z),
-                                               ctypes.byref(out_lk)))
+            if preprocessed is not None:
+                pcs.check(pcs.lib.eon_prove_air_pp(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                                   preprocessed.handle, ctypes.byref(a), ctypes.byref(z),
+                                                   ctypes.byref(out_pp)))
+            elif generic:
+                pcs.check(pcs.lib.eon_prove_air(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, ctypes.byref(a),
+                                                ctypes.byref(z), ctypes.byref(out)))
+            else:
+                pcs.check(pcs.lib.eon_prove_p2air(pcs._h, air.handle, tp, int(t.shape[0]), ctypes.byref(a),
+                                                  ctypes.byref(z), max_constraint_degree, coll, ctypes.byref(out)))
         else:
             a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
-            c_out = np.zeros((air.num_challenges, 4), np.uint64)
-            pcs.check(pcs.lib.eon_prove_air_lk_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, pph, ptp,
-                                                  challenger.handle, ctypes.byref(out_lk), _p(c_out), _p(a_out),
-                                                  _p(z_out)))
-            unm = lambda v: fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v)))  # noqa: E731
-            alpha, zeta, chal = unm(a_out), unm(z_out), [unm(c) for c in c_out]
-    elif challenger is None:
-        a, z = fr_to_abi(alpha), fr_to_abi(zeta)
-        if preprocessed is not None:
-            pcs.check(pcs.lib.eon_prove_air_pp(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
-                                               preprocessed.handle, ctypes.byref(a), ctypes.byref(z),
-                                               ctypes.byref(out_pp)))
-        elif generic:
-            pcs.check(pcs.lib.eon_prove_air(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, ctypes.byref(a),
-                                            ctypes.byref(z), ctypes.byref(out)))
-        else:
-            pcs.check(pcs.lib.eon_prove_p2air(pcs._h, air.handle, tp, int(t.shape[0]), ctypes.byref(a),
-                                              ctypes.byref(z), max_constraint_degree, coll, ctypes.byref(out)))
-    else:
-        a_out, z_out = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
-        if preprocessed is not None:
-            pcs.check(pcs.lib.eon_prove_air_pp_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
-                                                  preprocessed.handle, challenger.handle, ctypes.byref(out_pp),
-                                                  _p(a_out), _p(z_out)))
-        elif generic:
-            if collective is not None:
-                raise ValueError("the generic AIR path is not lane-sharded")
-            pcs.check(pcs.lib.eon_prove_air_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
-                                               challenger.handle, ctypes.byref(out), _p(a_out), _p(z_out)))
-        else:
-            pcs.check(pcs.lib.eon_prove_p2air_fs(pcs._h, air.handle, tp, int(t.shape[0]), challenger.handle,
-                                                 max_constraint_degree, coll, ctypes.byref(out), _p(a_out),
-                                                 _p(z_out)))
-        alpha = fr_unmont(sum(int(v) << (64 * i) for i, v in enumerate(a_out)))
-        zeta = fr_unmont(sum(int(v) << (64 * i) for i, v in enumerate(z_out)))
+            if preprocessed is not None:
+                pcs.check(pcs.lib.eon_prove_air_pp_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                                      preprocessed.handle, challenger.handle, ctypes.byref(out_pp),
+                                                      _p(a_out), _p(z_out)))
+            elif generic:
+                if collective is not None:
+                    raise ValueError("the generic AIR path is not lane-sharded")
+                pcs.check(pcs.lib.eon_prove_air_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                                   challenger.handle, ctypes.byref(out), _p(a_out), _p(z_out)))
+            else:
+                pcs.check(pcs.lib.eon_prove_p2air_fs(pcs._h, air.handle, tp, int(t.shape[0]), challenger.handle,
+                                                     max_constraint_degree, coll, ctypes.byref(out), _p(a_out),
+                                                     _p(z_out)))
+            alpha = fr_unmont(sum(int(v) << (64 * i) for i, v in enumerate(a_out)))
+            zeta = fr_unmont(sum(int(v) << (64 * i) for i, v in enumerate(z_out)))
     opened_trace = Opened(values=[[to[0], to[1]]], witnesses=[[tw[0], tw[1]]])
     opened_quot = Opened(values=[[qo[c:c + 1]] for c in range(chunks)], witnesses=[[qw[c:c + 1]] for c in range(chunks)])
     timings = {name: out.stage_ms[i] for i, name in enumerate(STAGES)}
@@ -681,5 +752,8 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         opened.insert(1, Opened(values=[[mo[0], mo[1]]], witnesses=[[mw[0], mw[1]]]))
     if preprocessed is not None:
         opened.append(Opened(values=[[po[0], po[1]]], witnesses=[[pw[0], pw[1]]]))
+    if batched and challenger is not None:
+        gamma, delta = pcs.last_opening_challenges()
     return Proof([tc], [qc[c:c + 1] for c in range(chunks)], opened, out.degree_bits, timings, alpha, zeta,
-                 [pc] if preprocessed is not None else None, [mc] if lookups else None, chal if lookups else None)
+                 [pc] if preprocessed is not None else None, [mc] if lookups else None, chal if lookups else None,
+                 opening, gamma if batched else None, delta if batched else None)

@@ -31,6 +31,13 @@ class Proof:
     # permutation, quotient chunks, preprocessed
     permutation_commit: object = None
     permutation_challenges: list | None = None
+    # the opening mode: "per_column" (the reference's KzgProof: one witness per column and point) or
+    # "batched" (one witness per matrix and point: opened[r].witnesses[m][t] is then (1, 8)), with the
+    # opening challenges used (canonical ints; delta is None after a prove with fixed challenges
+    # that was given none)
+    opening: str = "per_column"
+    gamma: int | None = None
+    delta: int | None = None
 
 
 class VerificationError(Exception):
