@@ -84,7 +84,8 @@ enum {
     EON_E_ARG = -5,              /* null pointer / invalid argument */
     EON_E_CONSTRAINT = -6,       /* the prove driver's constraint check failed (eon_prove.h; the reference's
                                     debug-build panic, check_constraints.rs:165-173) */
-    EON_E_SRS = -7               /* a supplied SRS was rejected; the eon_srs_report says why */
+    EON_E_SRS = -7,              /* a supplied SRS was rejected; the eon_srs_report says why */
+    EON_E_FORMAT = -8            /* proof bytes were rejected (eon_prove.h); the eon_proof_io_report says why */
 };
 
 enum {
@@ -247,6 +248,7 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   14: eon_g1_compress[_dev], the inverse of eon_g1_decompress[_dev], and EON_E_FORMAT, additive;
  *   13: eon_fr_fold_columns_dev, the gamma-fold of the batched KZG opening, additive;
  *   12: loading a supplied SRS -- eon_g1_decompress[_dev], eon_g1_validate_dev, eon_kzg_srs_check,
  *       eon_srs_report and EON_E_SRS, additive;
@@ -790,6 +792,16 @@ enum {
 int eon_g1_decompress_dev(eon_ctx* ctx, const uint8_t* bytes, uint64_t n, eon_g1_affine* out,
                           eon_srs_report* report);
 int eon_g1_decompress(eon_ctx* ctx, const uint8_t* bytes, uint64_t n, eon_g1_affine* out, eon_srs_report* report);
+/* G1Affine::to_bytes on the device, the exact inverse of eon_g1_decompress_dev and byte for byte
+ * eon_g1_to_bytes (eon_prove.h) of every accepted point, one point per lane: `pts` = n affine points,
+ * Montgomery (device, 16-byte aligned), `bytes` = n x 32 bytes (device, 16-byte aligned).  Per point:
+ * (0,0) -> 31 zero bytes and 0x40; otherwise both coordinates leave Montgomery form, x is stored
+ * little-endian and bit 7 of byte 31 is set when the canonical y is odd.  A coordinate >= q is
+ * NOT_CANONICAL (lowest index reported, EON_E_SRS) and that point is written as 32 zero bytes.  No
+ * curve test: to_bytes has none.  Synchronous like eon_g1_decompress_dev; n == 0 is valid.
+ * eon_g1_compress is the same on host arrays. */
+int eon_g1_compress_dev(eon_ctx* ctx, const eon_g1_affine* pts, uint64_t n, uint8_t* bytes, eon_srs_report* report);
+int eon_g1_compress(eon_ctx* ctx, const eon_g1_affine* pts, uint64_t n, uint8_t* bytes, eon_srs_report* report);
 /* Uncompressed SRS powers (device): both coordinates < q (else NOT_CANONICAL), not (0,0)
  * (IDENTITY), y^2 = x^3 + 3 (else NOT_ON_CURVE).  G1 has cofactor 1, so on the curve is in the
  * group.  Synchronous like eon_g1_decompress_dev. */

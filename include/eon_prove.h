@@ -387,10 +387,102 @@ int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_p
                       const eon_g1_affine* vk_commitment, eon_challenger* challenger, int* result,
                       eon_fr* challenges_out, eon_fr* alpha_out, eon_fr* zeta_out);
 
+/* ---- proof bytes --------------------------------------------------------------------------------
+ * A proof written down: the reference's Proof / Commitments / OpenedValues and KZG proof types derive
+ * Serialize / Deserialize (eon-uni-stark/src/proof.rs:17-44, kzg/src/pcs.rs:21-98).  The ELEMENT
+ * encodings are the reference's: an Fr is the 32 raw bytes of its Montgomery representation,
+ * little-endian -- the bytes of eon_fr -- and a value >= r does not deserialise
+ * (bn254/src/field.rs:188-207); a G1 is G1Affine::to_bytes, 32 compressed bytes, and an invalid point
+ * does not deserialise (bn254/src/curve.rs:84-98) -- eon_g1_to_bytes / eon_g1_decompress_dev.  The
+ * FRAMING is this project's own (serde's container format is the caller's choice in the reference and
+ * pinned nowhere), as EONSRS1 is for an SRS.  All integers little-endian:
+ *     0  magic "EONPRF1\0"
+ *     8  u32 version = 1
+ *    12  u32 flags: EON_PROOF_BATCHED | EON_PROOF_PREPROCESSED | EON_PROOF_PERMUTATION, every other bit zero
+ *    16  u32 degree_bits
+ *    20  u32 W, u32 C, u32 Wp, u32 Wq    (Wp / Wq zero exactly when their flag is clear)
+ *    36  u32 zero
+ *    40  u64 body length
+ *    48  body, the sections EON_PROOF_SECTION_* in their numeric order (proof.rs:19-44, the rounds of
+ *        prover.rs:426-439): commitments trace [W], permutation [Wq], quotient chunks [C]; opened values
+ *        trace_local [W], trace_next [W], permutation_local / _next [Wq], preprocessed_local / _next
+ *        [Wp], quotient chunks [C]; witnesses trace at zeta, at zeta h, permutation at zeta, at zeta h,
+ *        chunks [C], preprocessed at zeta, at zeta h -- each witness section but the chunks' has the
+ *        matrix's width in the per-column mode and ONE point in the batched mode (none when the part is
+ *        absent).
+ * Not in the bytes, as in the reference's Proof: the preprocessed commitment (the verifier key's; no
+ * verify reads the proof's copy), every challenge (a loaded proof is verified with a challenger,
+ * eon_verify_air_fs) and the timings.
+ *
+ * eon_proof_bytes_size: 48 + the body length of a shape, overflow-checked; 0 on an invalid shape.
+ * eon_proof_serialize: host only, no context -- eon_g1_to_bytes per point -- so a tool without a GPU
+ *   writes a proof.  Reads the arrays of `proof` at the lengths `shape` gives (preprocessed_commit and
+ *   proof->pp.base.degree_bits are not read: shape->degree_bits is written); *written receives the
+ *   size; cap below it or an invalid shape is EON_E_SHAPE; a NULL array that the shape needs, or an
+ *   opened value >= r, is EON_E_ARG.
+ * eon_proof_peek: host only; the header and the length.  The body length is recomputed from the
+ *   header's shape and compared with the stated one AND with len before anything else happens: one
+ *   byte short or one trailing byte is a rejection, and nothing is allocated.
+ * eon_proof_deserialize: peek, then fills the caller's arrays, sized from peek's shape
+ *   (preprocessed_commit is untouched and may be NULL; degree_bits is set).  Every opened value must
+ *   be < r (FR_NOT_CANONICAL); ALL points of the proof are decompressed and checked on the device in
+ *   one upload and one eon_g1_decompress call, whose report is mapped onto (reason, section, index in
+ *   the section).  When several elements are bad the one at the lowest byte offset is reported.  An
+ *   encoded identity is accepted and loads as (0,0): a constant column's witness and an all-zero
+ *   column's commitment are the identity.  After a rejection the arrays hold unspecified values.
+ * A rejection returns EON_E_FORMAT (eon.h) with *report filled (section EON_PROOF_SECTION_HEADER and
+ * index 0 for the header's reasons); EON_OK leaves reason = EON_PROOF_IO_OK. */
+enum { EON_PROOF_BATCHED = 1, EON_PROOF_PREPROCESSED = 2, EON_PROOF_PERMUTATION = 4 };
+enum {
+    EON_PROOF_IO_OK = 0,
+    EON_PROOF_IO_MAGIC = 1,
+    EON_PROOF_IO_VERSION = 2,
+    EON_PROOF_IO_FLAGS = 3,  /* an unknown flag bit, a width that contradicts its flag, the reserved word */
+    EON_PROOF_IO_LENGTH = 4, /* fewer than 48 bytes, or stated / actual length != the shape's */
+    EON_PROOF_IO_FR_NOT_CANONICAL = 5,
+    EON_PROOF_IO_G1_ENCODING = 6,      /* identity flag with other bits set */
+    EON_PROOF_IO_G1_NOT_CANONICAL = 7, /* x >= q */
+    EON_PROOF_IO_G1_NOT_ON_CURVE = 8   /* x^3 + 3 is no square */
+};
+enum {
+    EON_PROOF_SECTION_HEADER = 0,
+    EON_PROOF_SECTION_TRACE_COMMIT = 1,
+    EON_PROOF_SECTION_PERMUTATION_COMMIT = 2,
+    EON_PROOF_SECTION_QUOTIENT_COMMIT = 3,
+    EON_PROOF_SECTION_TRACE_LOCAL = 4,
+    EON_PROOF_SECTION_TRACE_NEXT = 5,
+    EON_PROOF_SECTION_PERMUTATION_LOCAL = 6,
+    EON_PROOF_SECTION_PERMUTATION_NEXT = 7,
+    EON_PROOF_SECTION_PREPROCESSED_LOCAL = 8,
+    EON_PROOF_SECTION_PREPROCESSED_NEXT = 9,
+    EON_PROOF_SECTION_QUOTIENT_OPENED = 10,
+    EON_PROOF_SECTION_TRACE_WITNESS_ZETA = 11,
+    EON_PROOF_SECTION_TRACE_WITNESS_NEXT = 12,
+    EON_PROOF_SECTION_PERMUTATION_WITNESS_ZETA = 13,
+    EON_PROOF_SECTION_PERMUTATION_WITNESS_NEXT = 14,
+    EON_PROOF_SECTION_QUOTIENT_WITNESS = 15,
+    EON_PROOF_SECTION_PREPROCESSED_WITNESS_ZETA = 16,
+    EON_PROOF_SECTION_PREPROCESSED_WITNESS_NEXT = 17
+};
+typedef struct {
+    uint32_t flags, degree_bits, width, chunks, pre_width, perm_width;
+} eon_proof_shape;
+typedef struct {
+    uint32_t reason, section;
+    uint64_t index;
+} eon_proof_io_report;
+uint64_t eon_proof_bytes_size(const eon_proof_shape* shape);
+int eon_proof_serialize(const eon_proof_lk* proof, const eon_proof_shape* shape, uint8_t* out, uint64_t cap,
+                        uint64_t* written);
+int eon_proof_peek(const uint8_t* bytes, uint64_t len, eon_proof_shape* shape, eon_proof_io_report* report);
+int eon_proof_deserialize(eon_ctx* ctx, const uint8_t* bytes, uint64_t len, eon_proof_lk* out,
+                          eon_proof_io_report* report);
+
 /* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
  * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; 8:
  * eon_kzg_pcs_create_from_srs[_bytes] and eon_kzg_pcs_create_verifier; 9: the opening mode,
- * eon_kzg_pcs_set_opening and its challenges; all additive) */
+ * eon_kzg_pcs_set_opening and its challenges; 10: the proof bytes, eon_proof_bytes_size / _serialize /
+ * _peek / _deserialize; all additive) */
 uint32_t eon_prove_abi_version(void);
 
 #ifdef __cplusplus

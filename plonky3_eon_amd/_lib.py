@@ -20,6 +20,7 @@ EON_E_OOM = -4
 EON_E_ARG = -5
 EON_E_CONSTRAINT = -6
 EON_E_SRS = -7
+EON_E_FORMAT = -8
 EON_SRS_OK = 0
 EON_SRS_ENCODING = 1
 EON_SRS_NOT_CANONICAL = 2
@@ -33,7 +34,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 13  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 14  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -43,6 +44,7 @@ _ERRNAMES = {
     EON_E_ARG: "EON_E_ARG",
     EON_E_CONSTRAINT: "EON_E_CONSTRAINT",
     EON_E_SRS: "EON_E_SRS",
+    EON_E_FORMAT: "EON_E_FORMAT",
 }
 
 
@@ -181,6 +183,8 @@ SIGNATURES = {
     "eon_g1_srs_powers_dev": (_INT, [_P, _P, _U64, _P]),
     "eon_g1_decompress_dev": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
     "eon_g1_decompress": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
+    "eon_g1_compress_dev": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
+    "eon_g1_compress": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
     "eon_g1_validate_dev": (_INT, [_P, _P, _U64, ctypes.POINTER(eon_srs_report)]),
     "eon_kzg_srs_check": (_INT, [_P, _P, _U64, _P, _P, ctypes.POINTER(eon_srs_report)]),
     "eon_selectors_on_coset_dev": (_INT, [_P, _U32, _U32, _P, _P]),

@@ -66,6 +66,9 @@ Status srs_dev(eon_ctx* ctx, const eon_fr* alpha, uint64_t n, G1Affine* out) {
 //                    by one fixed chain of 2-bit windows (the exponent is a constant, so every
 //                    branch of the chain is uniform over the wave: no divergence, and a rejected
 //                    lane runs the chain on whatever it holds and stores (0,0)), y^2 == t, parity
+//   k_g1_compress    the inverse, one affine point per lane: both coordinates out of Montgomery
+//                    form (one product by 1 each), x as two 16-byte stores with y's parity in bit
+//                    255; (0,0) -> the identity flag; a coordinate >= q is rejected, 32 zero bytes
 //   k_g1_validate    one affine point per lane: coordinates < q, not (0,0), on the curve
 //   k_rho_columns    the n x 2 matrix (rho^0 .. rho^(n-2), 0 | 0, rho^0 .. rho^(n-2)) of the
 //                    structure check, one row pair per lane
@@ -167,6 +170,23 @@ __global__ void __launch_bounds__(SRS_THREADS) k_g1_decompress(const uint32_t* _
     if (reason != EON_SRS_OK) srs_reject(worst, i, reason);
 }
 
+__global__ void __launch_bounds__(SRS_THREADS) k_g1_compress(const G1Affine* __restrict__ pts, uint64_t n,
+                                                             uint4* __restrict__ out,
+                                                             unsigned long long* __restrict__ worst) {
+    const uint64_t i = (uint64_t)blockIdx.x * SRS_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const G1Affine p = ld_affine(pts + i);
+    const bool bad = !fq_lt_q(p.x) || !fq_lt_q(p.y), inf = is_inf(p);
+    const Fq x = to_canonical(p.x), y = to_canonical(p.y);
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = bad || inf ? 0u : x.v[j];  // x < q < 2^254: bits 254, 255 are free
+    if (!bad) w[7] |= inf ? 0x40000000u : (y.v[0] & 1u) << 31;
+    out[2 * i] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[2 * i + 1] = make_uint4(w[4], w[5], w[6], w[7]);
+    if (bad) srs_reject(worst, i, EON_SRS_NOT_CANONICAL);
+}
+
 __global__ void __launch_bounds__(SRS_THREADS) k_g1_validate(const G1Affine* __restrict__ pts, uint64_t n,
                                                              unsigned long long* __restrict__ worst) {
     const uint64_t i = (uint64_t)blockIdx.x * SRS_THREADS + threadIdx.x;
@@ -249,6 +269,19 @@ Status decompress_dev(eon_ctx* ctx, const uint8_t* bytes, uint64_t n, G1Affine* 
     });
 }
 
+Status compress_dev(eon_ctx* ctx, const G1Affine* pts, uint64_t n, uint8_t* bytes, eon_srs_report* report) {
+    if (n > (1ull << 27)) return Status::err(EON_E_SHAPE, "at most 2^27 points");
+    if (n == 0) return Status::ok();
+    if ((reinterpret_cast<uintptr_t>(bytes) | reinterpret_cast<uintptr_t>(pts)) & 15)
+        return Status::err(EON_E_ARG, "points and compressed bytes must be 16-byte aligned");
+    return per_point_check(ctx, report, [&](unsigned long long* worst) {
+        ctx->prof.begin("k_g1_compress", n * (64 + 32), ctx->stream);
+        hipLaunchKernelGGL(k_g1_compress, dim3((unsigned)((n + SRS_THREADS - 1) / SRS_THREADS)), dim3(SRS_THREADS), 0,
+                           ctx->stream, pts, n, reinterpret_cast<uint4*>(bytes), worst);
+        ctx->prof.end(ctx->stream);
+    });
+}
+
 bool g2_abi_is_zero(const eon_g2_affine& q) {
     uint64_t acc = 0;
     for (int k = 0; k < 2; k++)
@@ -302,6 +335,41 @@ int eon_g1_decompress(eon_ctx* ctx, const uint8_t* bytes, uint64_t n, eon_g1_aff
         const Status d = decompress_dev(ctx, in.as<uint8_t>(), n, pts.as<G1Affine>(), report);
         if (d.bad() && d.code != EON_E_SRS) return d;
         EON_HIP(hipMemcpyAsync(out, pts.p, n * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return d;
+    }();
+    if (s.bad()) ctx->last_error = s.msg;
+    return s.code;
+}
+
+int eon_g1_compress_dev(eon_ctx* ctx, const eon_g1_affine* pts, uint64_t n, uint8_t* bytes, eon_srs_report* report) {
+    if (!ctx || !report) return EON_E_ARG;
+    *report = eon_srs_report{};
+    if (n && (!pts || !bytes)) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = compress_dev(ctx, reinterpret_cast<const G1Affine*>(pts), n, bytes, report);
+    if (s.bad()) ctx->last_error = s.msg;
+    return s.code;
+}
+
+int eon_g1_compress(eon_ctx* ctx, const eon_g1_affine* pts, uint64_t n, uint8_t* bytes, eon_srs_report* report) {
+    if (!ctx || !report) return EON_E_ARG;
+    *report = eon_srs_report{};
+    if (n && (!pts || !bytes)) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (n > (1ull << 27)) return Status::err(EON_E_SHAPE, "at most 2^27 points");
+        if (n == 0) return Status::ok();
+        DevBuf in, out;
+        PoolScope ps(ctx->pool, ctx->stream);
+        EON_HIP(ps.take(in, n * sizeof(G1Affine)));
+        EON_HIP(ps.take(out, n * 32));
+        EON_HIP(hipMemcpyAsync(in.p, pts, n * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+        const Status d = compress_dev(ctx, in.as<G1Affine>(), n, out.as<uint8_t>(), report);
+        if (d.bad() && d.code != EON_E_SRS) return d;
+        EON_HIP(hipMemcpyAsync(bytes, out.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return d;
     }();

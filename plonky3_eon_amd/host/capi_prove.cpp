@@ -107,7 +107,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 9; }
+uint32_t eon_prove_abi_version(void) { return 10; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;

@@ -23,7 +23,7 @@ from . import _lib
 from .collective import ALL_GATHER_FN, TorchCollective, eon_collective  # noqa: F401 (re-exported)
 from .dft import Context, default_context
 from .field import fr_to_abi, fr_unmont
-from .proof import Opened, Proof, VerificationError, log_quotient_degree  # noqa: F401 (re-exported)
+from .proof import Opened, Proof, ProofFormatError, VerificationError, log_quotient_degree  # noqa: F401 (re-exported)
 
 PROVE_LIB_PATH = Path(__file__).resolve().parent / "libeonprove.so"
 
@@ -55,6 +55,18 @@ class eon_proof_lk(ctypes.Structure):
     _fields_ = [("pp", eon_proof_pp), ("permutation_commit", _P), ("permutation_opened", _P),
                 ("permutation_witnesses", _P)]
 
+
+class eon_proof_shape(ctypes.Structure):
+    _fields_ = [(k, _U32) for k in ("flags", "degree_bits", "width", "chunks", "pre_width", "perm_width")]
+
+
+class eon_proof_io_report(ctypes.Structure):
+    _fields_ = [("reason", _U32), ("section", _U32), ("index", _U64)]
+
+
+EON_PROOF_BATCHED = 1
+EON_PROOF_PREPROCESSED = 2
+EON_PROOF_PERMUTATION = 4
 
 # name -> (restype, argtypes): every entry point of include/eon_prove.h
 SIGNATURES = {
@@ -103,6 +115,12 @@ SIGNATURES = {
     "eon_prove_air_pp_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_pp), _P, _P]),
     "eon_prove_air_lk": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, _U32, _P, _P, ctypes.POINTER(eon_proof_lk)]),
     "eon_prove_air_lk_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, _P, ctypes.POINTER(eon_proof_lk), _P, _P, _P]),
+    "eon_proof_bytes_size": (_U64, [ctypes.POINTER(eon_proof_shape)]),
+    "eon_proof_serialize": (_INT, [ctypes.POINTER(eon_proof_lk), ctypes.POINTER(eon_proof_shape), _P, _U64,
+                                   ctypes.POINTER(_U64)]),
+    "eon_proof_peek": (_INT, [_P, _U64, ctypes.POINTER(eon_proof_shape), ctypes.POINTER(eon_proof_io_report)]),
+    "eon_proof_deserialize": (_INT, [_P, _P, _U64, ctypes.POINTER(eon_proof_lk),
+                                     ctypes.POINTER(eon_proof_io_report)]),
     "eon_verify_air": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _P, _U32, _U32, _U32, _P, _P, _U32, _P, _P,
                               ctypes.POINTER(_INT)]),
     "eon_verify_air_fs": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _P, _U32, _U32, _U32, _P, _P,
@@ -612,6 +630,147 @@ def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: 
     if res.value != 0:
         raise VerificationError(VerificationError.KINDS[res.value], pcs.lib.eon_kzg_pcs_last_error(pcs._h).decode())
     return None
+
+
+def proof_shape(proof) -> eon_proof_shape:
+    """The eon_proof_shape of a Proof, read off its arrays."""
+    if proof.opening not in OPENING_MODES:
+        raise ValueError(f"unknown opening mode {proof.opening!r}")
+    has_perm = proof.permutation_commit is not None
+    has_pre = len(proof.opened) > (3 if has_perm else 2)
+    flags = (EON_PROOF_BATCHED if proof.opening == "batched" else 0) | (EON_PROOF_PREPROCESSED if has_pre else 0) | \
+        (EON_PROOF_PERMUTATION if has_perm else 0)
+    rows = lambda a: np.asarray(a).reshape(-1, 4).shape[0]  # noqa: E731
+    return eon_proof_shape(flags, int(proof.degree_bits), np.asarray(proof.trace_commit[0]).reshape(-1, 8).shape[0],
+                           len(proof.quotient_commit), rows(proof.opened[-1].values[0][0]) if has_pre else 0,
+                           rows(proof.opened[1].values[0][0]) if has_perm else 0)
+
+
+def _proof_arrays(shape: eon_proof_shape):
+    """Zeroed arrays of a shape and the eon_proof_lk over them (the arrays keep it alive)."""
+    batched = bool(shape.flags & EON_PROOF_BATCHED)
+    w, c, wp, wq = shape.width, shape.chunks, shape.pre_width, shape.perm_width
+    a = {"tc": np.zeros((w, 8), np.uint64), "qc": np.zeros((c, 8), np.uint64), "to": np.zeros((2, w, 4), np.uint64),
+         "tw": np.zeros((2, 1 if batched else w, 8), np.uint64), "qo": np.zeros((c, 4), np.uint64),
+         "qw": np.zeros((c, 8), np.uint64)}
+    if wp:
+        a["po"] = np.zeros((2, wp, 4), np.uint64)
+        a["pw"] = np.zeros((2, 1 if batched else wp, 8), np.uint64)
+    if wq:
+        a["mc"] = np.zeros((wq, 8), np.uint64)
+        a["mo"] = np.zeros((2, wq, 4), np.uint64)
+        a["mw"] = np.zeros((2, 1 if batched else wq, 8), np.uint64)
+    return a
+
+
+def _proof_lk(a, degree_bits: int) -> eon_proof_lk:
+    ptr = lambda k: _p(a[k]) if k in a else None  # noqa: E731
+    base = eon_proof(_p(a["tc"]), _p(a["qc"]), _p(a["to"]), _p(a["tw"]), _p(a["qo"]), _p(a["qw"]), int(degree_bits))
+    return eon_proof_lk(eon_proof_pp(base, None, ptr("po"), ptr("pw")), ptr("mc"), ptr("mo"), ptr("mw"))
+
+
+def _proof_io_check(rc: int, rep: eon_proof_io_report, what: str):
+    if rc == _lib.EON_E_FORMAT:
+        raise ProofFormatError(int(rep.reason), int(rep.section), int(rep.index))
+    _check(rc, what)
+
+
+def proof_to_bytes(proof) -> bytes:
+    """Proof.to_bytes: eon_proof_serialize over the proof's arrays (host only)."""
+    lib = load()
+    shape = proof_shape(proof)
+    a = _proof_arrays(shape)
+    has_perm, has_pre = "mc" in a, "po" in a
+
+    def fill(dst, src, what):
+        src = np.asarray(src, dtype=np.uint64)
+        if src.size != dst.size:
+            raise ValueError(f"{what}: {src.size // dst.shape[-1]} entries, the proof's shape has "
+                             f"{dst.size // dst.shape[-1]}")
+        dst[...] = src.reshape(dst.shape)
+
+    def fill_pair(vals, wits, op, what):
+        if len(op.values) != 1 or len(op.values[0]) != 2 or len(op.witnesses) != 1 or len(op.witnesses[0]) != 2:
+            raise ValueError(f"{what}: one matrix opened at two points expected")
+        for t in range(2):
+            fill(vals[t], op.values[0][t], f"{what} values")
+            fill(wits[t], op.witnesses[0][t], f"{what} witnesses")
+
+    opened = list(proof.opened)
+    fill(a["tc"], proof.trace_commit[0], "trace commitment")
+    fill(a["qc"], np.stack([np.asarray(c, dtype=np.uint64).reshape(8) for c in proof.quotient_commit]),
+         "quotient commitment")
+    fill_pair(a["to"], a["tw"], opened[0], "trace")
+    quot = opened[2 if has_perm else 1]
+    if len(quot.values) != shape.chunks or len(quot.witnesses) != shape.chunks:
+        raise ValueError(f"{len(quot.values)} quotient chunks opened, {shape.chunks} committed")
+    fill(a["qo"], np.stack([np.asarray(v[0], dtype=np.uint64).reshape(4) for v in quot.values]), "quotient values")
+    fill(a["qw"], np.stack([np.asarray(w[0], dtype=np.uint64).reshape(8) for w in quot.witnesses]),
+         "quotient witnesses")
+    if has_perm:
+        fill(a["mc"], proof.permutation_commit[0], "permutation commitment")
+        fill_pair(a["mo"], a["mw"], opened[1], "permutation")
+    if has_pre:
+        fill_pair(a["po"], a["pw"], opened[-1], "preprocessed")
+    lk = _proof_lk(a, shape.degree_bits)
+    size = lib.eon_proof_bytes_size(ctypes.byref(shape))
+    if size == 0:
+        raise ValueError("the proof's shape is not serialisable")
+    out = np.zeros(size, np.uint8)
+    written = _U64(0)
+    _check(lib.eon_proof_serialize(ctypes.byref(lk), ctypes.byref(shape), _p(out), size, ctypes.byref(written)),
+           "eon_proof_serialize")
+    return out[:written.value].tobytes()
+
+
+def proof_peek(data) -> eon_proof_shape:
+    """eon_proof_peek: the shape in the header of proof bytes, after the header and length checks
+    (host only).  Raises ProofFormatError."""
+    lib = load()
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    shape, rep = eon_proof_shape(), eon_proof_io_report()
+    _proof_io_check(lib.eon_proof_peek(_p(buf) if buf.size else None, buf.size, ctypes.byref(shape),
+                                       ctypes.byref(rep)), rep, "eon_proof_peek")
+    return shape
+
+
+def proof_from_bytes(data, ctx: Context | None = None) -> Proof:
+    """Proof.from_bytes: eon_proof_peek for the shape, then eon_proof_deserialize into fresh arrays."""
+    lib = load()
+    raw = bytes(data)
+    shape = proof_peek(raw)
+    ctx = ctx or default_context(0)
+    buf = np.frombuffer(raw, dtype=np.uint8)
+    a = _proof_arrays(shape)
+    lk = _proof_lk(a, 0)
+    rep = eon_proof_io_report()
+    ctx.set_stream(None)
+    rc = lib.eon_proof_deserialize(ctx.handle, _p(buf), buf.size, ctypes.byref(lk), ctypes.byref(rep))
+    if rc not in (0, _lib.EON_E_FORMAT):
+        ctx.check(rc)
+    _proof_io_check(rc, rep, "eon_proof_deserialize")
+    chunks = shape.chunks
+    opened = [Opened(values=[[a["to"][0], a["to"][1]]], witnesses=[[a["tw"][0], a["tw"][1]]]),
+              Opened(values=[[a["qo"][c:c + 1]] for c in range(chunks)],
+                     witnesses=[[a["qw"][c:c + 1]] for c in range(chunks)])]
+    if "mc" in a:
+        opened.insert(1, Opened(values=[[a["mo"][0], a["mo"][1]]], witnesses=[[a["mw"][0], a["mw"][1]]]))
+    if "po" in a:
+        opened.append(Opened(values=[[a["po"][0], a["po"][1]]], witnesses=[[a["pw"][0], a["pw"][1]]]))
+    return Proof([a["tc"]], [a["qc"][c:c + 1] for c in range(chunks)], opened, int(lk.pp.base.degree_bits),
+                 permutation_commit=[a["mc"]] if "mc" in a else None,
+                 opening="batched" if shape.flags & EON_PROOF_BATCHED else "per_column")
+
+
+def verify_native_bytes(prog, pcs: NativeKzgPcs, data, public_values=(), challenger: Challenger | None = None,
+                        preprocessed_vk=None, transcript: dict | None = None) -> None:
+    """Proof.from_bytes(data) followed by verify_native: a proof that arrived as bytes.  The bytes
+    carry no challenge, so a `challenger` is required.  ProofFormatError when the bytes do not
+    deserialise (before any verification), VerificationError as verify_native."""
+    if challenger is None:
+        raise ValueError("proof bytes carry no challenges: verify them with a challenger")
+    proof = proof_from_bytes(data, pcs.ctx)
+    return verify_native(prog, pcs, proof, public_values, challenger, preprocessed_vk, transcript)
 
 
 def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | None,

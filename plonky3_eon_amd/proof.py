@@ -1,6 +1,12 @@
 """The proof the native driver returns (libeonprove.so, native.prove_native), in the reference's
 shape: eon-uni-stark/src/proof.rs:19-44 (commitments, opened values, opening proof, degree bits)
-with KzgPcs's per-column witnesses (kzg/src/pcs.rs:289-335)."""
+with KzgPcs's per-column witnesses (kzg/src/pcs.rs:289-335).
+
+``Proof.to_bytes`` / ``from_bytes`` / ``save`` / ``load`` are the proof container of
+include/eon_prove.h ("proof bytes": eon_proof_serialize / eon_proof_deserialize).  The bytes hold the
+commitments, opened values and witnesses; the preprocessed commitment (the verifier key's), every
+challenge and the timings are not in them, so a loaded proof is verified with a challenger
+(native.verify_native_bytes)."""
 
 from __future__ import annotations
 
@@ -38,6 +44,51 @@ class Proof:
     opening: str = "per_column"
     gamma: int | None = None
     delta: int | None = None
+
+    def to_bytes(self) -> bytes:
+        """The proof container (eon_proof_serialize): host only, no GPU needed."""
+        from .native import proof_to_bytes
+
+        return proof_to_bytes(self)
+
+    @classmethod
+    def from_bytes(cls, data, ctx=None) -> "Proof":
+        """eon_proof_deserialize: every opened value checked < r, every point decompressed and
+        checked on the device in one call.  Raises ProofFormatError(reason, section, index).  The
+        loaded proof has preprocessed_commit None and every challenge None."""
+        from .native import proof_from_bytes
+
+        return proof_from_bytes(data, ctx)
+
+    def save(self, path) -> None:
+        with open(path, "wb") as f:
+            f.write(self.to_bytes())
+
+    @classmethod
+    def load(cls, path, ctx=None) -> "Proof":
+        with open(path, "rb") as f:
+            return cls.from_bytes(f.read(), ctx)
+
+
+class ProofFormatError(Exception):
+    """Proof bytes that do not deserialise (EON_E_FORMAT).  Not a VerificationError: the reference
+    fails in serde before its verifier runs.  `reason` is one of REASONS, `section` one of SECTIONS
+    ("HEADER" for the header's reasons) and `index` the element's index within that section."""
+
+    REASONS = ["OK", "MAGIC", "VERSION", "FLAGS", "LENGTH", "FR_NOT_CANONICAL", "G1_ENCODING", "G1_NOT_CANONICAL",
+               "G1_NOT_ON_CURVE"]
+    SECTIONS = ["HEADER", "TRACE_COMMIT", "PERMUTATION_COMMIT", "QUOTIENT_COMMIT", "TRACE_LOCAL", "TRACE_NEXT",
+                "PERMUTATION_LOCAL", "PERMUTATION_NEXT", "PREPROCESSED_LOCAL", "PREPROCESSED_NEXT",
+                "QUOTIENT_OPENED", "TRACE_WITNESS_ZETA", "TRACE_WITNESS_NEXT", "PERMUTATION_WITNESS_ZETA",
+                "PERMUTATION_WITNESS_NEXT", "QUOTIENT_WITNESS", "PREPROCESSED_WITNESS_ZETA",
+                "PREPROCESSED_WITNESS_NEXT"]
+
+    def __init__(self, reason, section=0, index: int = 0):
+        self.reason = self.REASONS[reason] if isinstance(reason, int) else reason
+        self.section = self.SECTIONS[section] if isinstance(section, int) else section
+        self.index = int(index)
+        where = "" if self.section == "HEADER" else f" at {self.section}[{self.index}]"
+        super().__init__(f"proof bytes rejected: {self.reason}{where}")
 
 
 class VerificationError(Exception):

@@ -6,6 +6,7 @@ input of KzgPcs::from_srs (kzg/src/pcs.rs:170-175).
                                       as (16,) limbs in the eon_g2_affine layout; ``max_degree = n - 1``.
 * ``Srs.unsafe(max_degree, alpha)``-- init_srs_unsafe (params.rs:123-139) from a known trapdoor: tests.
 * ``g1_decompress(bytes)``         -- eon_g1_decompress: the device's inverse of g1_to_bytes.
+* ``g1_compress(points)``          -- eon_g1_compress: g1_to_bytes of every point in one device call.
 * ``g1_validate(points)``          -- eon_g1_validate_dev on uploaded points.
 * ``srs_check(bases, n, g2, rho)`` -- eon_kzg_srs_check over an MsmBases table.
 * ``Srs.save`` / ``Srs.load``      -- this project's own container (no ceremony format is read):
@@ -94,6 +95,19 @@ def g1_decompress(data, ctx: Context | None = None) -> np.ndarray:
     return out
 
 
+def g1_compress(points, ctx: Context | None = None) -> bytes:
+    """(n, 8) affine points -> n x 32 compressed bytes (eon_g1_compress): eon_g1_to_bytes of every
+    point, one lane each; (0,0) is the identity.  SrsError("NOT_CANONICAL", index) names the lowest
+    point with a coordinate >= q."""
+    ctx = ctx or default_context(0)
+    p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+    n = p.shape[0]
+    out = np.zeros(max(n, 1) * 4, dtype=np.uint64)
+    rep = _lib.eon_srs_report()
+    check_report(ctx, ctx.lib.eon_g1_compress(ctx.handle, _p(p), n, _p(out), ctypes.byref(rep)), rep)
+    return out.view(np.uint8)[:32 * n].tobytes()
+
+
 def g1_validate(points, ctx: Context | None = None) -> None:
     """eon_g1_validate_dev on (n, 8) affine points (uploaded): canonical, on the curve, no identity."""
     import torch
@@ -163,13 +177,21 @@ class Srs:
             raise SrsError("CONTAINER", 0, f"max_degree {max_degree} needs {k} powers, the SRS has {self.n}")
         return Srs(self.g1_bytes[:32 * k] if self.compressed else self.g1_powers[:k], self.g2_alpha)
 
-    def compress(self) -> "Srs":
-        """The same SRS with its G1 powers as compressed bytes (eon_g1_to_bytes per point)."""
+    def compress(self, ctx: Context | None = None) -> "Srs":
+        """The same SRS with its G1 powers as compressed bytes: eon_g1_to_bytes of every point, in
+        ONE g1_compress call on the device.  Only a host with no GPU at all (a tool that writes a
+        container, like eon_proof_serialize) takes the host's eon_g1_to_bytes per point instead; with
+        a device present a failing kernel is an error, never that loop."""
         if self.compressed:
             return self
-        from .native import g1_to_bytes
+        if ctx is None:
+            import torch
 
-        return Srs(b"".join(g1_to_bytes(p) for p in self.g1_powers), self.g2_alpha)
+            if not torch.cuda.is_available():
+                from .native import g1_to_bytes
+
+                return Srs(b"".join(g1_to_bytes(p) for p in self.g1_powers), self.g2_alpha)
+        return Srs(g1_compress(self.g1_powers, ctx), self.g2_alpha)
 
     def save(self, path, compressed: bool = True) -> None:
         if compressed:
