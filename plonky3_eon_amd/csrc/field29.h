@@ -298,17 +298,15 @@ EON_HD void mul29_vs(uint64_t& acc, uint32_t a, uint32_t b) {
 }
 
 // One column's terms: acc (= 0 when FIRST) + sum va[i] vb[i] + sum sa[i] sb[i], sb wave-uniform
-// (SGPRs).  With EON_MAD_BLOCKS (default) the terms go out as one asm statement per up to 9 + 9
-// of them (mad_blocks.h): the compiler puts an s_nop between any two adjacent asm statements,
+// (SGPRs).  On the device the terms go out as one asm statement per up to 9 + 9 of them
+// (mad_blocks.h): the compiler puts an s_nop between any two adjacent asm statements,
 // which cost 11-16 % of a chain's throughput as one statement per term
-// (profiles/r05/s11/ubench_mad_nop.txt).  Without it, one statement per term (mad29_vv / _vs).
-#ifndef EON_MAD_BLOCKS
-#define EON_MAD_BLOCKS 1
-#endif
+// (profiles/r05/s11/ubench_mad_nop.txt).  The host pass takes one statement per term
+// (mad29_vv / _vs).
 template <int NV, int NS, bool FIRST = false>
 EON_HD void madcol(uint64_t& acc, const uint32_t* va, const uint32_t* vb, const uint32_t* sa,
                    const uint32_t* sb) {
-#if defined(__HIP_DEVICE_COMPILE__) && EON_MAD_BLOCKS
+#ifdef __HIP_DEVICE_COMPILE__
     if constexpr (NV > 9) {
         MadAsm<9, 0, FIRST>::run(acc, va, vb, sa, sb);
         madcol<NV - 9, NS, false>(acc, va + 9, vb + 9, sa, sb);
@@ -623,20 +621,14 @@ EON_HD F29 shl5_to261(const Fe<M>& a) {
 }
 
 // a^2 2^-261 mod p (limbs < 2^30, a^2 < 0.99 p 2^261, as mul29): each column's cross products
-// once, summed apart and doubled by a shift (45 instead of 81 limb products; cross sums < 2^62)
-//
-// EON_SQR_DOUBLED (default): the cross products are taken against a doubled copy 2 a_i (i < 8,
-// limbs < 2^31) straight into the column's accumulator -- 8 limb doublings instead of one
-// shift-and-add of a separate cross sum per column (15); the column sums are the same numbers.
-#ifndef EON_SQR_DOUBLED
-#define EON_SQR_DOUBLED 1
-#endif
+// once (45 instead of 81 limb products), taken against a doubled copy 2 a_i (i < 8, limbs < 2^31)
+// straight into the column's accumulator -- 8 limb doublings instead of one shift-and-add of a
+// separate cross sum per column (15); the column sums are the same numbers.
 template <class M, int U = 8>
 EON_HD F29 sqr29(const F29& a) {
     uint32_t m[9];
     F29 r;
     uint64_t acc;
-#if EON_SQR_DOUBLED
     uint32_t d[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) d[i] = a.l[i] << 1;
@@ -688,57 +680,6 @@ EON_HD F29 sqr29(const F29& a) {
     });
     r.l[8] = (uint32_t)acc;
     return r;
-#else
-    static_for<0, 9>([&](auto kc) {
-        constexpr int k = EON_K(kc), nc = (k + 1) / 2, nq = (k & 1) ? 0 : 1;
-        if constexpr (nc > 0) {
-            uint64_t cross;
-            uint32_t va[nc], vb[nc];
-#pragma unroll
-            for (int i = 0; i < nc; i++) {
-                va[i] = a.l[i];
-                vb[i] = a.l[k - i];
-            }
-            madcol<nc, 0, true>(cross, va, vb, nullptr, nullptr);
-            acc += cross << 1;
-        }
-        uint32_t va[1] = {a.l[k / 2]}, sa[k + 1], sb[k + 1];
-#pragma unroll
-        for (int i = 0; i < k; i++) {
-            sa[i] = m[i];
-            sb[i] = R29<M>::P[k - i];
-        }
-        madcol<nq, k, k == 0>(acc, va, va, sa, sb);
-        m[k] = k < U ? (uint32_t)acc * R29<M>::INV : ((uint32_t)acc * R29<M>::INV) & M29;
-        mad29_vs(acc, m[k], R29<M>::P[0]);
-        acc >>= 29;
-    });
-    static_for<9, 17>([&](auto kc) {
-        constexpr int k = EON_K(kc), nc = (k - 1) / 2 - (k - 8) + 1, nq = (k & 1) ? 0 : 1, n = 17 - k;
-        if constexpr (nc > 0) {
-            uint64_t cross;
-            uint32_t va[nc], vb[nc];
-#pragma unroll
-            for (int i = 0; i < nc; i++) {
-                va[i] = a.l[k - 8 + i];
-                vb[i] = a.l[8 - i];
-            }
-            madcol<nc, 0, true>(cross, va, vb, nullptr, nullptr);
-            acc += cross << 1;
-        }
-        uint32_t va[1] = {a.l[k / 2]}, sa[n], sb[n];
-#pragma unroll
-        for (int i = k - 8; i < 9; i++) {
-            sa[i - (k - 8)] = m[i];
-            sb[i - (k - 8)] = R29<M>::P[k - i];
-        }
-        madcol<nq, n>(acc, va, va, sa, sb);
-        r.l[k - 9] = (uint32_t)acc & M29;
-        acc >>= 29;
-    });
-    r.l[8] = (uint32_t)acc;
-    return r;
-#endif
 }
 
 // (a b + c d) 2^-261 mod p with one reduction: 27 terms per column, so a, c and d must be
@@ -856,17 +797,14 @@ EON_HD F29 uniform29(const F29& a) {
 
 // Whole products as one asm statement each (prod_asm.h, generated by tools/gen_prod_asm.py): the
 // same column schedule and results as mul29 / sqr29 / mul29_sum2, without the wait state hipcc
-// puts after every asm statement (one per column above).  EON_PRODUCT_ASM=0 routes the *_x
-// entry points to the column-block versions (A/B).
-#ifndef EON_PRODUCT_ASM
-#define EON_PRODUCT_ASM 1
-#endif
+// puts after every asm statement (one per column above).  The *_x / *_ip entry points take them on
+// the device and the column versions on the host.
 }  // namespace eon
 #include "prod_asm.h"
 namespace eon {
 template <class M>
 EON_HD F29 mul29_x(const F29& a, const F29& b) {
-#if defined(__HIP_DEVICE_COMPILE__) && EON_PRODUCT_ASM
+#ifdef __HIP_DEVICE_COMPILE__
     return mul29_asm<M>(a, b);
 #else
     return mul29<M>(a, b);
@@ -874,7 +812,7 @@ EON_HD F29 mul29_x(const F29& a, const F29& b) {
 }
 template <class M>
 EON_HD F29 sqr29_x(const F29& a) {
-#if defined(__HIP_DEVICE_COMPILE__) && EON_PRODUCT_ASM && EON_SQR_DOUBLED
+#ifdef __HIP_DEVICE_COMPILE__
     return sqr29_asm<M>(a);
 #else
     return sqr29<M>(a);
@@ -882,7 +820,7 @@ EON_HD F29 sqr29_x(const F29& a) {
 }
 template <class M>
 EON_HD F29 mul29_sum2_x(const F29& a, const F29& b, const F29& c, const F29& d) {
-#if defined(__HIP_DEVICE_COMPILE__) && EON_PRODUCT_ASM
+#ifdef __HIP_DEVICE_COMPILE__
     return mul29_sum2_asm<M>(a, b, c, d);
 #else
     return mul29_sum2<M>(a, b, c, d);
@@ -891,7 +829,7 @@ EON_HD F29 mul29_sum2_x(const F29& a, const F29& b, const F29& c, const F29& d) 
 // in place: a = a b, c = a b + c d (a loop-carried accumulator updated without a register copy)
 template <class M>
 EON_HD void mul29_ip(F29& a, const F29& b) {
-#if defined(__HIP_DEVICE_COMPILE__) && EON_PRODUCT_ASM
+#ifdef __HIP_DEVICE_COMPILE__
     mul29_asm_ip<M>(a, b);
 #else
     a = mul29<M>(a, b);
@@ -899,7 +837,7 @@ EON_HD void mul29_ip(F29& a, const F29& b) {
 }
 template <class M>
 EON_HD void mul29_sum2_ip(const F29& a, const F29& b, F29& c, const F29& d) {
-#if defined(__HIP_DEVICE_COMPILE__) && EON_PRODUCT_ASM
+#ifdef __HIP_DEVICE_COMPILE__
     mul29_sum2_asm_ip<M>(a, b, c, d);
 #else
     c = mul29_sum2<M>(a, b, c, d);

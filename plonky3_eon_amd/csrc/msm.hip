@@ -74,18 +74,13 @@ namespace eon {
 // sorted pairs per k_piece_sum thread: 2^log_chunk, sized so a batch launches ~2^20 threads
 // (>= 4 waves on every SIMD) within [2^4, 2^7]
 constexpr uint32_t LOG_CHUNK_MIN = 4, LOG_CHUNK_MAX = 7;
-// a batch's chunks grow while its piece sums keep >= 2^EON_PIECE_THREADS_LOG threads
-#ifndef EON_PIECE_THREADS_LOG
-#define EON_PIECE_THREADS_LOG 20
-#endif
+// a batch's chunks grow while its piece sums keep >= 2^PIECE_THREADS_LOG threads
+constexpr uint32_t PIECE_THREADS_LOG = 20;
 constexpr uint32_t PIECE = 32;   // partials per combine step
 constexpr uint32_t SEG = 8;     // buckets per reduction segment
 // buckets per segment of the call-wide (deferred-finish) reduction: k_bucket_reduce29 walks RED_SEG
 // buckets per lane, k_group_finish29 combines B / RED_SEG segments per group
-#ifndef EON_RED_SEG
-#define EON_RED_SEG 8
-#endif
-constexpr uint32_t RED_SEG = EON_RED_SEG;
+constexpr uint32_t RED_SEG = 8;
 constexpr uint32_t TREE = 256;  // points per tree-reduction block
 constexpr uint32_t FINISH_THREADS = 256;  // threads per group of k_group_finish / k_group_finish29
 
@@ -297,62 +292,6 @@ struct DigitSource {
     }
 };
 
-// The lean tile's source (EON_SORT_LEAN, sort_pass.h): LEAN_THREADS x 2 pairs per tile, i.e.
-// LEAN_THREADS / 8 rows of one column; thread t takes row r0 + t % R and the windows 2 (t / R),
-// 2 (t / R) + 1 (R = LEAN_THREADS / 8), both in the scalar's word t / R.  The carry into window 2j
-// of the signed recoding is 1 exactly when the scalar's low 32 j bits exceed 0x8000...8000 (every
-// 16-bit window at 2^15: the largest low part the digits [-(2^15 - 1), 2^15] represent), a
-// comparison the words below decide from the top -- almost always word j - 1 alone.
-struct DigitSourceLean {
-    const Fr* canon;
-    uint64_t n;
-    uint32_t tiles_per_col, ref_windows;
-    template <bool FULL, uint32_t THREADS, uint32_t ITEMS>
-    __device__ __forceinline__ void load(uint32_t tile, uint32_t w, uint32_t lane, uint32_t, uint32_t (&key)[ITEMS],
-                                         uint32_t (&val)[ITEMS]) const {
-        static_assert(ITEMS == 2, "two 16-bit windows per thread");
-        constexpr uint32_t R = THREADS / 8;  // rows per tile
-        const uint32_t t = w * 64 + lane;
-        const uint32_t col = tile / tiles_per_col;
-        const uint64_t i = (uint64_t)(tile - col * tiles_per_col) * R + t % R;
-        const uint32_t j = t / R;  // the scalar's word: windows 2 j, 2 j + 1
-        const uint32_t* s = reinterpret_cast<const uint32_t*>(canon + (uint64_t)col * n + i);
-        const uint32_t word = s[j];
-        uint32_t carry = 0;
-        for (int k = (int)j - 1; k >= 0; k--) {  // low part > 0x8000..8000 ?
-            const uint32_t x = s[k];
-            if (x != 0x80008000u) {
-                carry = x > 0x80008000u;
-                break;
-            }
-        }
-#pragma unroll
-        for (uint32_t h = 0; h < 2; h++) {
-            const uint32_t raw = ((word >> (16 * h)) & 0xffffu) + carry;
-            uint32_t mag, neg;
-            if (raw > (1u << 15)) {
-                mag = (1u << 16) - raw;
-                neg = 1;
-                carry = 1;
-            } else {
-                mag = raw;
-                neg = 0;
-                carry = 0;
-            }
-            key[h] = mag ? (col << 16 | (mag - 1)) : 0xFFFFFFFFu;
-            val[h] = mag ? ((uint32_t)(i * ref_windows + 2 * j + h) | neg << 31) : 0u;
-        }
-    }
-};
-
-__global__ void __launch_bounds__(sortpass::LEAN_THREADS) k_digit_sort_pass_lean(DigitSourceLean src, uint32_t* kd,
-                                                                                 uint32_t* vd, uint32_t n, uint32_t shift,
-                                                                                 const uint32_t* base, uint64_t* status,
-                                                                                 uint32_t* tile_ctr) {
-    sortpass::sort_pass_tile<8, DigitSourceLean, sortpass::LEAN_THREADS, sortpass::LEAN_ITEMS>(src, kd, vd, n, shift, 8,
-                                                                                             base, status, tile_ctr);
-}
-
 __global__ void __launch_bounds__(sortpass::SORT_THREADS) k_digit_sort_pass(DigitSource src, uint32_t* kd, uint32_t* vd,
                                                                             uint32_t n, uint32_t shift,
                                                                             const uint32_t* base, uint64_t* status,
@@ -442,20 +381,10 @@ __global__ void k_piece_owner(const uint32_t* piece_off, uint32_t nb, uint32_t* 
     for (uint32_t p = piece_off[b]; p < piece_off[b + 1]; p++) owner[p] = b;
 }
 
-#ifndef EON_PIECE_MINWAVES
-#define EON_PIECE_MINWAVES 4
-#endif
-// EON_PIECE_NEGSUM=0 builds the round-5 loop (madd29_unchecked, radix-2^32 base negation): A/B
-#ifndef EON_PIECE_NEGSUM
-#define EON_PIECE_NEGSUM 1
-#endif
-// EON_PIECE_MERGE: the two pieces of every bucket straddling one chunk boundary are summed into
-// the first before k_bucket_reduce29, which then reads one piece for such a bucket -- 2 (default):
-// by k_piece_sum29's lane t for the boundary with lane t + 1 of its wave, and by k_piece_merge29
-// for the boundaries between waves; 1: all by k_piece_merge29; 0: the reduction sums them itself
-#ifndef EON_PIECE_MERGE
-#define EON_PIECE_MERGE 2
-#endif
+constexpr uint32_t PIECE_MINWAVES = 4;  // k_piece_sum29's waves per SIMD (its VGPR budget: 128)
+// The two pieces of every bucket straddling one chunk boundary are summed into the first before
+// k_bucket_reduce29, which then reads one piece for such a bucket: by k_piece_sum29's lane t for
+// the boundary with lane t + 1 of its wave, and by k_piece_merge29 for the boundaries between waves
 
 // Thread t sums the sorted pairs [t 2^log_chunk, (t+1) 2^log_chunk) (nonzero digits only): one
 // partial per bucket run, stored at piece_off[b] + t - (start[b] >> log_chunk).  The XYZZ
@@ -463,7 +392,7 @@ __global__ void k_piece_owner(const uint32_t* piece_off, uint32_t nb, uint32_t* 
 // bases are read in 29-Montgomery form (k_table_to29).  Each bucket run stores its raw accumulator (144 bytes,
 // ZZ = 0 for the identity); k_raw29_to_xyzz converts the pieces for the combine levels.
 //
-// The additions are unchecked (madd29_unchecked): x(acc) == x(A) -- a duplicate base, or a base
+// The additions are unchecked (madd29_negsum): x(acc) == x(A) -- a duplicate base, or a base
 // meeting its negation -- leaves ZZ = 0 mod p for the rest of the run, so the run's ZZ is tested
 // once at its flush and such a run is summed again with the checked additions (piece_run29).
 // An identity base ((0, 0) in the table) is recognised by y = 0 alone: G1 has prime order, so no
@@ -493,7 +422,7 @@ __device__ __forceinline__ bool piece_run29(const uint32_t* vals, const G1Affine
     return inf;
 }
 
-__global__ void __launch_bounds__(64, EON_PIECE_MINWAVES) k_piece_sum29(
+__global__ void __launch_bounds__(64, PIECE_MINWAVES) k_piece_sum29(
     const uint32_t* keys, const uint32_t* vals, const uint32_t* start, const uint32_t* piece_off,
     uint32_t log_chunk, uint32_t c, uint32_t groups, uint32_t nb, const G1Affine* pts29, G1Raw29* piece_raw) {
     // the nonzero-digit pairs (start[nb]): read here, so that the launch need not wait for the
@@ -507,47 +436,30 @@ __global__ void __launch_bounds__(64, EON_PIECE_MINWAVES) k_piece_sum29(
         uint32_t run = e0;  // first pair of the current bucket run
         G1X29 acc;
         bool inf = true;
-#if EON_PIECE_NEGSUM
         // the accumulator holds (-1)^flip times the run's sum (madd29_negsum returns the negated
         // sum; a run opening with a negative digit starts from the unnegated base with flip set)
         bool flip = false;
-#endif
         auto flush = [&](uint32_t e_end) __attribute__((always_inline)) {
             if (!inf && is_zero_mod29<FqP>(acc.ZZ)) {
                 inf = piece_run29(vals, pts29, run, e_end, acc);
-#if EON_PIECE_NEGSUM
                 flip = false;
-#endif
             }
-#if EON_PIECE_NEGSUM
             if (flip) acc.ZZZ = neg29_lazy<3>(acc.ZZZ);  // ZZZ < 2p normalised -> 3p - ZZZ
-#endif
             const uint32_t bb = bucket_of(b, c, groups, nb);
             G1Raw29* dst = piece_raw + piece_off[bb] + t - (start[bb] >> log_chunk);
-#if EON_PIECE_NEGSUM
             // an identity piece is any raw accumulator with ZZ = 0 (every reader tests ZZ alone):
             // one store of acc either way, instead of selecting all 36 words between acc and zeros
             if (inf) acc.ZZ = F29{};
             st_raw29(dst, acc);
-#else
-            if (inf)
-                st_raw29_inf(dst);
-            else
-                st_raw29(dst, acc);
-#endif
         };
-#ifndef EON_PIECE_SCALAR_PAIRS
         // 16-byte loads of four keys and four references every fourth pair (chunks are aligned to
         // 2^LOG_CHUNK_MIN pairs; a chunk cut short by n_pairs reads one pair at a time): a quarter
-        // of the pair-stream requests (prove -2.5 % A/B; EON_PIECE_SCALAR_PAIRS restores the
-        // one-pair loads)
+        // of the pair-stream requests (prove -2.5 % A/B against one-pair loads)
         const bool vec = ((e0 | e1) & 3) == 0;
         uint4 kq = make_uint4(0, 0, 0, 0), vq = kq;
-#endif
         for (uint32_t e = e0;; e++) {
             // one flush site (the run's end or the chunk's), so the checked re-sum is emitted once
             const bool last = e == e1;
-#ifndef EON_PIECE_SCALAR_PAIRS
             // the pair is always picked from the register quads (a chunk cut short reloads
             // component 0 every pair): a pick written as "vec ? quad component : *p" was compiled
             // as one load through a selected pointer, which kept the quads in scratch (eight
@@ -566,9 +478,6 @@ __global__ void __launch_bounds__(64, EON_PIECE_MINWAVES) k_piece_sum29(
                 return sub == 0 ? q.x : sub == 1 ? q.y : sub == 2 ? q.z : q.w;
             };
             const uint32_t k = last ? b : pick(kq);
-#else
-            const uint32_t k = last ? b : keys[e];
-#endif
             if (last || k != b) {
                 flush(e);
                 if (last) break;
@@ -576,20 +485,9 @@ __global__ void __launch_bounds__(64, EON_PIECE_MINWAVES) k_piece_sum29(
                 b = k;
                 run = e;
             }
-#ifndef EON_PIECE_SCALAR_PAIRS
             const uint32_t v = pick(vq);
-#else
-            const uint32_t v = vals[e];
-#endif
-#ifdef EON_PIECE_PROBE_MASK
-            // memory-sensitivity probe (tuning builds only, wrong results): every gather from a
-            // cache-resident slice of the table
-            G1Affine a = ld_affine(pts29 + (v & EON_PIECE_PROBE_MASK));
-#else
             G1Affine a = ld_affine(pts29 + (v & 0x7fffffffu));
-#endif
             if (a.y.is_zero()) continue;
-#if EON_PIECE_NEGSUM
             // the digit's sign and the accumulator's are applied together, as one lazy negation of
             // the base's y in radix 2^29 (9 subtractions and 9 selects instead of a borrow chain)
             const bool neg_digit = v >> 31;
@@ -610,21 +508,7 @@ __global__ void __launch_bounds__(64, EON_PIECE_MINWAVES) k_piece_sum29(
                 madd29_negsum(acc, ax, ys);
                 flip = !flip;
             }
-#else
-            if (v >> 31) a.y = neg(a.y);
-            const F29 ax = unpack29(a.x), ay = unpack29(a.y);
-            if (inf) {
-                acc.X = ax;
-                acc.Y = ay;
-                acc.ZZ = const29<FqP>(R29<FqP>::ONE);
-                acc.ZZZ = acc.ZZ;
-                inf = false;
-            } else {
-                madd29_unchecked(acc, ax, ay);
-            }
-#endif
         }
-#if EON_PIECE_MERGE == 2
         // acc holds the chunk's last piece as stored.  When its bucket goes on into the next chunk
         // and ends there (two pieces), lane t + 1 of this wave stored the bucket's second piece
         // at its first flush -- earlier in this wave's instruction stream, every lane's pair loop
@@ -643,7 +527,6 @@ __global__ void __launch_bounds__(64, EON_PIECE_MINWAVES) k_piece_sum29(
                 st_raw29_inf(piece_raw + p0 + 1);
             }
         }
-#endif
     }
 }
 
@@ -753,7 +636,7 @@ __device__ __forceinline__ void st_point(G1Raw29* p, const G1X29& a, bool inf) {
 
 // Buckets whose pairs straddle exactly one chunk boundary hold two pieces (k_piece_sum29's thread
 // t - 1 ends the bucket's first run, thread t starts its second): here they are summed into the
-// first, one thread per chunk boundary, so that k_bucket_reduce29<.., true> reads one piece for
+// first, one thread per chunk boundary, so that k_bucket_reduce29 reads one piece for
 // every such bucket.  In the reduction a wave walks the buckets of a segment in step, one lane
 // per group, and pays the most pieces any lane has per bucket -- two almost always (a bucket of
 // ~64 sorted pairs straddles a 128-pair chunk boundary half of the time), so its three additions
@@ -783,7 +666,7 @@ __global__ void __launch_bounds__(64) k_piece_merge29(const uint32_t* keys, cons
         st_raw29(pieces + p0, a);
 }
 
-template <class OutT, bool MERGED = false>
+template <class OutT>
 __global__ void __launch_bounds__(64) k_bucket_reduce29(const G1Raw29* pieces, const uint32_t* piece_off,
                                                         uint32_t B, uint32_t seg, uint32_t groups, OutT* T,
                                                         OutT* U) {
@@ -797,7 +680,7 @@ __global__ void __launch_bounds__(64) k_bucket_reduce29(const G1Raw29* pieces, c
         const uint32_t bp = (s * seg + (uint32_t)k) * groups + g;
         const uint32_t e0 = piece_off[bp];
         uint32_t e1 = piece_off[bp + 1];
-        if (MERGED && e1 - e0 == 2) e1 = e0 + 1;  // k_piece_merge29 summed the two into the first
+        if (e1 - e0 == 2) e1 = e0 + 1;  // k_piece_merge29 summed the two into the first
         for (uint32_t e = e0; e < e1; e++) {
             const bool inf = ld_raw29(pieces + e, x);
             acc29(run, run_inf, x, inf);
@@ -1291,17 +1174,15 @@ struct MsmLayout {
 // digit pairs per column batch: 2^29 (the prove's 1312 columns in 6 batches of <= 256, a rank's
 // 164 of the 8-way sharded prove in one): fewer, larger piece-sum launches than 2^28 -- prove
 // -0.5 %, emulated 8-rank prove -1 % (profiles/r05/s23, s24; 2^30 measured the same)
-#ifndef EON_MSM_BATCH_LOG_PAIRS
-#define EON_MSM_BATCH_LOG_PAIRS 29
-#endif
+constexpr uint32_t MSM_BATCH_LOG_PAIRS = 29;
 static MsmLayout msm_layout(const eon_msm_bases* b, uint64_t n, uint32_t width) {
     MsmLayout L;
     L.precomputed = b->precomputed;
     L.c = b->precomputed ? b->c : choose_c(n, false);
     L.W = (255 + L.c - 1) / L.c;
-    // columns per batch: keep the digit pairs of one batch at <= 2^EON_MSM_BATCH_LOG_PAIRS (8 GiB of
+    // columns per batch: keep the digit pairs of one batch at <= 2^MSM_BATCH_LOG_PAIRS (8 GiB of
     // sort buffers at 2^29)
-    uint64_t cpb = (1ull << EON_MSM_BATCH_LOG_PAIRS) / (n * L.W);
+    uint64_t cpb = (1ull << MSM_BATCH_LOG_PAIRS) / (n * L.W);
     if (cpb < 1) cpb = 1;
     const uint64_t max_groups = b->precomputed ? cpb : cpb * L.W;
     if (max_groups > 65535) cpb = b->precomputed ? 65535 : 65535 / L.W;
@@ -1321,18 +1202,6 @@ static std::vector<Batch> make_batches(const Fr* scalars, uint32_t width, uint64
         batches.push_back(bt);
     }
     return batches;
-}
-
-// EON_MSM_FUSED_SORT (default 1): the digit sort's first pass ranks the digits as k_digit_sort_pass
-// computes them (batch_sort); 0 restores k_msm_digits4 + two k_sort_pass passes
-#ifndef EON_MSM_FUSED_SORT
-#define EON_MSM_FUSED_SORT 1
-#endif
-
-// The digit sort: sort.hip's stable LSD radix sort (two 8-bit passes for c = 16)
-static hipError_t sort_pairs(void* temp, const uint32_t* k_in, uint32_t* k_out, const uint32_t* v_in,
-                             uint32_t* v_out, uint64_t n, uint32_t bits, hipStream_t st, bool hist_ready) {
-    return radix_sort_pairs(temp, k_in, k_out, v_in, v_out, n, bits, st, hist_ready);
 }
 
 // digits + radix sort + bucket starts + piece offsets of one batch into `out`; `wk` supplies the
@@ -1363,7 +1232,7 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
     bt.scan_bytes = exclusive_scan_temp_bytes(nb + 1);
     EON_HIP(ctx_ensure(ctx, wk.temp, std::max(bt.sort_bytes, bt.scan_bytes)));
     bt.log_chunk = LOG_CHUNK_MIN;
-    while (bt.log_chunk < LOG_CHUNK_MAX && (E >> (bt.log_chunk + 1)) >= (1ull << EON_PIECE_THREADS_LOG)) bt.log_chunk++;
+    while (bt.log_chunk < LOG_CHUNK_MAX && (E >> (bt.log_chunk + 1)) >= (1ull << PIECE_THREADS_LOG)) bt.log_chunk++;
     // few buckets for many pairs (a bucket would collect more than ~8 pieces): longer chunks while
     // the piece sums keep 2^18 threads (4 waves per SIMD)
     while (bt.log_chunk < LOG_CHUNK_MAX && (E >> bt.log_chunk) > 8ull * nb && (E >> (bt.log_chunk + 1)) >= (1ull << 18))
@@ -1384,8 +1253,7 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
     const uint32_t grid_x = (uint32_t)std::min<uint64_t>(tiles, std::max<uint32_t>(1, DIGIT_BLOCKS / grid_y));
     // the first sort pass fused with the digits (DigitSource): fixed-base tables, c = 16, all 16
     // windows, whole 1024-row tiles, two passes
-    const bool fused = EON_MSM_FUSED_SORT && L.precomputed && bt.c == 16 && bt.W == 16 && L.W == 16 &&
-                       n % (EON_SORT_LEAN ? sortpass::LEAN_THREADS / 8 : sortpass::SORT_THREADS) == 0 &&
+    const bool fused = L.precomputed && bt.c == 16 && bt.W == 16 && L.W == 16 && n % sortpass::SORT_THREADS == 0 &&
                        radix_sort_passes(bt.key_bits).passes == 2;
     if (fused) {
         EON_HIP(ctx_ensure(ctx, wk.canon, n * bt.cols * sizeof(Fr)));
@@ -1397,15 +1265,8 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
         EON_HIP(hipGetLastError());
         EON_HIP(radix_sort_prepare(wk.temp.p, E, bt.key_bits, st));
         const RadixPassArgs a0 = radix_sort_pass_args(wk.temp.p, E, bt.key_bits, 0);
-        // per call: the attribute is per device (another context may run on another GPU)
         // the pass's own traffic: 32 bytes of scalar per 16 pairs read, 8 bytes per pair written
         prof->begin("k_digit_sort_pass", n * bt.cols * 32 + E * 8, st);
-#if EON_SORT_LEAN
-        const DigitSourceLean src{wk.canon.as<Fr>(), n, (uint32_t)(n / (sortpass::LEAN_THREADS / 8)), L.W};
-        hipLaunchKernelGGL(k_digit_sort_pass_lean, dim3(a0.tiles), dim3(sortpass::LEAN_THREADS), sortpass::LEAN_LDS, st,
-                           src, wk.keys.as<uint32_t>(), wk.vals.as<uint32_t>(), (uint32_t)E, a0.shift, a0.base,
-                           a0.status, a0.tile_ctr);
-#else
         // per call: the attribute is per device (another context may run on another GPU)
         EON_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_digit_sort_pass),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sortpass::SORT_LDS));
@@ -1413,7 +1274,6 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
         hipLaunchKernelGGL(k_digit_sort_pass, dim3(a0.tiles), dim3(sortpass::SORT_THREADS), sortpass::SORT_LDS, st, src,
                            wk.keys.as<uint32_t>(), wk.vals.as<uint32_t>(), (uint32_t)E, a0.shift, a0.base, a0.status,
                            a0.tile_ctr);
-#endif
         prof->end(st);
         EON_HIP(hipGetLastError());
         prof->begin("radix_sort_pairs", E * 16, st);  // the second pass
@@ -1431,8 +1291,8 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
         EON_HIP(hipGetLastError());
         // every pass reads and writes each (key, value) pair once: 16 bytes per pair and pass
         prof->begin("radix_sort_pairs", E * 16 * radix_sort_passes(bt.key_bits).passes, st);
-        EON_HIP(sort_pairs(wk.temp.p, wk.keys.as<uint32_t>(), out.keys2.as<uint32_t>(), wk.vals.as<uint32_t>(),
-                           out.vals2.as<uint32_t>(), E, bt.key_bits, st, true));
+        EON_HIP(radix_sort_pairs(wk.temp.p, wk.keys.as<uint32_t>(), out.keys2.as<uint32_t>(), wk.vals.as<uint32_t>(),
+                                 out.vals2.as<uint32_t>(), E, bt.key_bits, st, true));
         prof->end(st);
     }
     prof->begin("k_bucket_start", E * 4, st);
@@ -1481,27 +1341,38 @@ static SortedRef sorted_ref(const SortedBufs& s) {
                      s.piece_off.as<uint32_t>()};
 }
 
-// the reduction reads k_piece_sum29's raw partials directly (k_bucket_reduce29 /
-// k_segment_reduce29): radix-2^29 pieces, no combine level needed, and either many groups or few
-// pieces per bucket -- with few groups and several pieces per bucket (a single 2^20 MSM: ~4.5)
-// the one-thread-per-segment chain is longer than combine + bucket-final + k_segment_sum
-// (3.23 vs 3.00 ms for the 2^20 MSM)
-static bool fused_reduce(const Batch& bt) {
-    return bt.levels <= 1 && bt.B >= SEG &&
-           (bt.groups >= 64 || (uint64_t)bt.n_pieces <= 2ull * bt.nb);
-}
+// The way a counted batch's pieces become one point per group (batch_reduce): the Fused routes and
+// Sums29 read k_piece_sum29's raw radix-2^29 pieces, the Combine routes their radix-2^32 conversion
+// (k_raw29_to_xyzz, batch_pieces); the Groups routes and Deferred end in a group finish, the
+// Segments routes and Sums29 in LDS trees.
+enum class Reduce { Deferred, FusedGroups, FusedSegments, Sums29, CombineGroups, CombineSegments };
 
-// few groups, several pieces per bucket, none above PIECE: k_bucket_sums29 + k_segment_sum29
-// (round 5; the combine-level path stays for skewed inputs, whose buckets hold more pieces)
-#ifndef EON_MSM_SUMS29
-#define EON_MSM_SUMS29 1
-#endif
-static bool sums_reduce(const Batch& bt) {
-    return EON_MSM_SUMS29 && bt.levels <= 1 && bt.B >= SEG && bt.groups < 64 && !fused_reduce(bt);
+static Reduce reduce_route(const Batch& bt, const MsmLayout& L, bool deferred_available) {
+    const bool one_level = bt.levels <= 1 && bt.B >= SEG;  // no bucket holds more than PIECE pieces
+    // batches with < 64 groups (a single MSM) use the shorter-chain k_segment_sum (running sums +
+    // lo * run) + k_tree_sum: there latency, not additions, sets the time
+    const bool few_groups = bt.groups < 64;
+    // the reduction reads k_piece_sum29's raw partials directly (k_bucket_reduce29 /
+    // k_segment_reduce29): radix-2^29 pieces, no combine level needed, and either many groups or few
+    // pieces per bucket -- with few groups and several pieces per bucket (a single 2^20 MSM: ~4.5)
+    // the one-thread-per-segment chain is longer than combine + bucket-final + k_segment_sum
+    // (3.23 vs 3.00 ms for the 2^20 MSM)
+    if (one_level && (!few_groups || (uint64_t)bt.n_pieces <= 2ull * bt.nb)) {
+        if (few_groups) return Reduce::FusedSegments;
+        // first level only; the finish runs once per call (run_deferred_finish)
+        if (deferred_available && bt.B >= RED_SEG && L.precomputed) return Reduce::Deferred;
+        return Reduce::FusedGroups;
+    }
+    // few groups, several pieces per bucket, none above PIECE: k_bucket_sums29 + k_segment_sum29
+    // (round 5; the combine-level path stays for skewed inputs, whose buckets hold more pieces)
+    if (one_level && few_groups) return Reduce::Sums29;
+    // combine levels until every bucket holds one partial (skewed scalars put many pieces in a
+    // bucket: all-equal scalars put n pieces in one bucket per window)
+    return few_groups ? Reduce::CombineSegments : Reduce::CombineGroups;
 }
 
 // piece sums of one sorted batch against bases `b` (asynchronous); wk supplies the piece buffers
-static Status batch_pieces(eon_ctx* ctx, const eon_msm_bases* b, Batch& bt, const SortedRef& sr,
+static Status batch_pieces(eon_ctx* ctx, const MsmLayout& L, const eon_msm_bases* b, Batch& bt, const SortedRef& sr,
                            MsmWork& wk, hipStream_t st) {
     EON_HIP(ctx_ensure(ctx, wk.piece_sums, std::max<uint64_t>(bt.max_pieces * sizeof(G1Xyzz), (uint64_t)bt.nb * sizeof(G1Raw29))));
     EON_HIP(ctx_ensure(ctx, wk.piece_sums2, bt.max_pieces * sizeof(G1Xyzz)));
@@ -1532,7 +1403,9 @@ static Status batch_pieces(eon_ctx* ctx, const eon_msm_bases* b, Batch& bt, cons
                            bt.log_chunk, bt.c, bt.groups, bt.nb, pts, wk.piece_raw.as<G1Raw29>());
     ctx->prof.end(st);
     if (!bt.counted) EON_TRY(batch_counts(ctx, bt, wk, msm_n));
-    if (bt.n_pieces && !fused_reduce(bt) && !sums_reduce(bt))
+    // the Combine routes (chosen alike with or without a deferred finish) sum radix-2^32 pieces
+    const Reduce route = reduce_route(bt, L, false);
+    if (bt.n_pieces && (route == Reduce::CombineGroups || route == Reduce::CombineSegments))
         hipLaunchKernelGGL(k_raw29_to_xyzz, dim3(blocks_for(bt.n_pieces, 128)), dim3(128), 0, st,
                            wk.piece_raw.as<G1Raw29>(), bt.n_pieces, wk.piece_sums.as<G1Xyzz>());
     EON_HIP(hipGetLastError());
@@ -1554,40 +1427,26 @@ static Status write_columns(const MsmLayout& L, const Batch& bt, const G1Xyzz* p
     return Status::ok();
 }
 
-// sum_d d * B_d per group, few-groups form: k_segment_sum + LDS trees (short dependency chains)
-static Status reduce_segments(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
-                              MsmWork& wk, hipStream_t st, bool fused, bool sums29 = false) {
+// sum_d d * B_d per group, few-groups form: k_segment_sum + LDS trees (short dependency chains).
+// The segment routes open alike: the two segment buffers and the k_segment_sum record
+static Status begin_segments(eon_ctx* ctx, const Batch& bt, MsmWork& wk, hipStream_t st) {
     const uint32_t nseg = bt.B / SEG;  // c >= 4, so B >= SEG
-    const uint32_t groups = bt.groups;
-    EON_HIP(ctx_ensure(ctx, wk.red_a, (uint64_t)groups * nseg * sizeof(G1Xyzz)));
-    EON_HIP(ctx_ensure(ctx, wk.red_b, (uint64_t)groups * nseg * sizeof(G1Xyzz)));
-    ctx->prof.begin("k_segment_sum", (uint64_t)bt.nb * 128 + (uint64_t)groups * nseg * 128, st);
-    if (sums29) {
-        // raw bucket sums (k_bucket_sums29, in wk.piece_sums as G1Raw29) -> one raw partial per
-        // 256 segments -> one point per group, all in radix 2^29
-        const uint32_t seg = std::min(bt.B, seg29_for((uint64_t)bt.B * groups));
-        const uint32_t bpg = (bt.B / seg + SEG_BLOCK - 1) / SEG_BLOCK;
-        EON_HIP(ctx_ensure(ctx, wk.red_b, (uint64_t)groups * bpg * sizeof(G1Raw29)));
-        hipLaunchKernelGGL(k_segment_sum29, dim3(groups * bpg), dim3(SEG_BLOCK), 0, st, wk.piece_sums.as<G1Raw29>(),
-                           bt.B, seg, bpg, wk.red_b.as<G1Raw29>());
-        hipLaunchKernelGGL(k_tree_sum29, dim3(groups), dim3(SEG_BLOCK), 0, st, wk.red_b.as<G1Raw29>(), bpg,
-                           wk.red_a.as<G1Xyzz>());
-        ctx->prof.end(st);
-        EON_HIP(hipGetLastError());
-        return write_columns(L, bt, wk.red_a.as<G1Xyzz>(), st);
-    } else if (fused)
-        hipLaunchKernelGGL(k_segment_reduce29, dim3(blocks_for((uint64_t)nseg * groups, 64)), dim3(64), 0, st,
-                           wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, groups, wk.red_a.as<G1Xyzz>());
-    else
-        hipLaunchKernelGGL(k_segment_sum, dim3(blocks_for((uint64_t)nseg * groups, 64)), dim3(64), 0, st,
-                           wk.bucket_sums.as<G1Xyzz>(), bt.B, groups, wk.red_a.as<G1Xyzz>());
+    EON_HIP(ctx_ensure(ctx, wk.red_a, (uint64_t)bt.groups * nseg * sizeof(G1Xyzz)));
+    EON_HIP(ctx_ensure(ctx, wk.red_b, (uint64_t)bt.groups * nseg * sizeof(G1Xyzz)));
+    ctx->prof.begin("k_segment_sum", (uint64_t)bt.nb * 128 + (uint64_t)bt.groups * nseg * 128, st);
+    return Status::ok();
+}
+
+// closes the k_segment_sum record; B / SEG segment sums per group in wk.red_a -> k_tree_sum levels
+// -> the columns
+static Status tree_sum_segments(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, MsmWork& wk, hipStream_t st) {
     ctx->prof.end(st);
     G1Xyzz* cur = wk.red_a.as<G1Xyzz>();
     G1Xyzz* nxt = wk.red_b.as<G1Xyzz>();
-    uint32_t len = nseg;
+    uint32_t len = bt.B / SEG;
     while (len > 1) {
         const uint32_t blk = (len + TREE - 1) / TREE;
-        hipLaunchKernelGGL(k_tree_sum, dim3(blk, groups), dim3(TREE), 0, st, cur, len, nxt);
+        hipLaunchKernelGGL(k_tree_sum, dim3(blk, bt.groups), dim3(TREE), 0, st, cur, len, nxt);
         std::swap(cur, nxt);
         len = blk;
     }
@@ -1608,10 +1467,14 @@ struct DeferredFinish {
     std::vector<std::pair<uint64_t, uint64_t>> rows;  // deferred [row0, row0 + n)
 };
 
-// k_group_finish over the deferred rows (merged into maximal runs) on `st`
 static hipError_t launch_group_finish29(const G1Raw29* T, const G1Raw29* U, uint32_t nseg, uint32_t lsg,
-                                        G1Xyzz* out, uint32_t groups, hipStream_t st);
+                                        G1Xyzz* out, uint32_t groups, hipStream_t st) {
+    hipLaunchKernelGGL(k_group_finish29<FINISH_THREADS>, dim3(groups), dim3(FINISH_THREADS), 0, st, T, U, nseg, lsg,
+                       out);
+    return hipGetLastError();
+}
 
+// k_group_finish over the deferred rows (merged into maximal runs) on `st`
 static Status run_deferred_finish(eon_ctx* ctx, DeferredFinish& df, hipStream_t st) {
     if (df.rows.empty()) return Status::ok();
     std::sort(df.rows.begin(), df.rows.end());
@@ -1649,9 +1512,8 @@ static Status prepare_deferred(eon_ctx* ctx, const MsmLayout& L, uint64_t rows, 
 }
 
 static Status piece_merge(eon_ctx* ctx, const Batch& bt, const SortedRef& sr, MsmWork& wk, hipStream_t st) {
-    if (!EON_PIECE_MERGE) return Status::ok();
     const uint64_t chunks = ((uint64_t)bt.n_pairs + (1u << bt.log_chunk) - 1) >> bt.log_chunk;
-    const uint32_t log_step = EON_PIECE_MERGE == 2 ? 6 : 0;
+    const uint32_t log_step = 6;  // the boundaries between k_piece_sum29's waves (k_piece_merge29)
     const uint64_t boundaries = (chunks - 1) >> log_step;
     if (chunks < 2 || boundaries == 0) return Status::ok();
     // ~one addition per boundary: 2 x 144 B read, 144 B written
@@ -1663,44 +1525,17 @@ static Status piece_merge(eon_ctx* ctx, const Batch& bt, const SortedRef& sr, Ms
     return Status::ok();
 }
 
-// combine levels, bucket sums and the weighted bucket reduction of one batch's pieces (read-back
-// of each level's count synchronises `st`); leaves one XYZZ point per column at bt.out.  The
-// sorted piece offsets are only read (a prepared batch is reduced once per bases object).
-static Status batch_reduce(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
-                           MsmWork& wk, hipStream_t st, bool fused, DeferredFinish* df = nullptr) {
-    Profiler* prof = &ctx->prof;
-    const uint32_t nb = bt.nb, groups = bt.groups, B = bt.B;
-    if (df && df->T && fused && groups >= 64 && B >= RED_SEG && L.precomputed) {
-        // first level only; the finish runs once per call (run_deferred_finish)
-        const uint64_t row0 = (uint64_t)(bt.out - df->out_base);
-        EON_TRY(piece_merge(ctx, bt, sr, wk, st));
-        prof->begin("bucket_reduce", (uint64_t)nb * 128 + (uint64_t)nb / SEG * 256, st);
-        hipLaunchKernelGGL((k_bucket_reduce29<G1Raw29, EON_PIECE_MERGE != 0>),
-                           dim3(blocks_for((uint64_t)df->nseg * groups, 64)), dim3(64), 0, st,
-                           wk.piece_raw.as<G1Raw29>(), sr.piece_off, B, RED_SEG, groups, df->T + row0 * df->nseg,
-                           df->U + row0 * df->nseg);
-        prof->end(st);
-        EON_HIP(hipGetLastError());
-        df->rows.emplace_back(row0, groups);
-        return Status::ok();
-    }
-    if (!fused && sums_reduce(bt)) {
-        prof->begin("k_bucket_sums29", (uint64_t)bt.n_pieces * 144 + (uint64_t)nb * 144, st);
-        hipLaunchKernelGGL(k_bucket_sums29, dim3(blocks_for(nb, 256)), dim3(256), 0, st, wk.piece_raw.as<G1Raw29>(),
-                           sr.piece_off, B, groups, wk.piece_sums.as<G1Raw29>());
-        prof->end(st);
-        EON_HIP(hipGetLastError());
-        return reduce_segments(ctx, L, bt, sr, wk, st, false, true);
-    }
-    // combine levels until every bucket holds one partial (skewed scalars put many pieces in a
-    // bucket: all-equal scalars put n pieces in one bucket per window)
+// combine levels until every bucket holds one partial, then the bucket sums (wk.bucket_sums,
+// group-major) of the Combine routes
+static Status combine_levels(eon_ctx* ctx, const Batch& bt, const SortedRef& sr, MsmWork& wk, hipStream_t st) {
+    const uint32_t nb = bt.nb;
     const uint32_t* off_cur = sr.piece_off;
     uint32_t* off_bufs[2] = {wk.off2.as<uint32_t>(), wk.off3.as<uint32_t>()};
     int next_off = 0;
     G1Xyzz* part_cur = wk.piece_sums.as<G1Xyzz>();
     G1Xyzz* part_nxt = wk.piece_sums2.as<G1Xyzz>();
     uint64_t bound = bt.n_pieces;  // >= the partials of the current level
-    for (uint32_t level = 0; level < (fused ? 0u : bt.levels); level++) {
+    for (uint32_t level = 0; level < bt.levels; level++) {
         uint32_t* off_nxt = off_bufs[next_off];
         hipLaunchKernelGGL(k_level_count, dim3(blocks_for(nb + 1, 256)), dim3(256), 0, st, off_cur,
                            nb, wk.count.as<uint32_t>());
@@ -1709,47 +1544,139 @@ static Status batch_reduce(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, co
                            wk.owner.as<uint32_t>());
         // sum_b ceil(p_b / PIECE) <= min(bound, nb + bound / PIECE)
         const uint64_t nxt = std::min<uint64_t>(bound, nb + bound / PIECE);
-        prof->begin("k_partial_combine", (bound + nxt) * 128, st, (bound - std::min(bound, nxt)) * 14);
+        ctx->prof.begin("k_partial_combine", (bound + nxt) * 128, st, (bound - std::min(bound, nxt)) * 14);
         hipLaunchKernelGGL(k_partial_combine, dim3(blocks_for(nxt, 64)), dim3(64), 0, st, off_cur, off_nxt,
                            wk.owner.as<uint32_t>(), nb, part_cur, part_nxt);
-        prof->end(st);
+        ctx->prof.end(st);
         off_cur = off_nxt;
         next_off ^= 1;
         std::swap(part_cur, part_nxt);
         bound = nxt;
     }
-    if (!fused)
-        hipLaunchKernelGGL(k_bucket_final, dim3(blocks_for(nb, 256)), dim3(256), 0, st, off_cur, B, groups,
-                           part_cur, wk.bucket_sums.as<G1Xyzz>());
-    if (groups < 64) return reduce_segments(ctx, L, bt, sr, wk, st, fused);
-    // sum_d d * B_d per group (bucket b holds digit b + 1): segment sums T, U of SEG buckets
-    // (k_bucket_reduce29 from the raw pieces, or k_seg_level from bucket sums), then k_group_finish
-    G1Xyzz* T = wk.piece_sums.as<G1Xyzz>();
-    G1Xyzz* u_buf = wk.piece_sums2.as<G1Xyzz>();
-    EON_HIP(wk.red_a.ensure((uint64_t)groups * sizeof(G1Xyzz)));
-    prof->begin("bucket_reduce", (uint64_t)nb * 128 + (uint64_t)nb / SEG * 256, st);
-    const uint32_t seg = B < SEG ? B : SEG;
-    const uint32_t nseg = B / seg;
-    if (fused) {
-        EON_TRY(piece_merge(ctx, bt, sr, wk, st));
-        hipLaunchKernelGGL((k_bucket_reduce29<G1Xyzz, EON_PIECE_MERGE != 0>), dim3(blocks_for((uint64_t)nseg * groups, 64)),
-                           dim3(64), 0, st, wk.piece_raw.as<G1Raw29>(), sr.piece_off, B, seg, groups, T, u_buf);
-    } else
-        hipLaunchKernelGGL(k_seg_level, dim3(blocks_for((uint64_t)nseg * groups, 64)), dim3(64), 0, st,
-                           wk.bucket_sums.as<G1Xyzz>(), B, seg, groups, T, u_buf);
+    hipLaunchKernelGGL(k_bucket_final, dim3(blocks_for(nb, 256)), dim3(256), 0, st, off_cur, bt.B, bt.groups,
+                       part_cur, wk.bucket_sums.as<G1Xyzz>());
+    return Status::ok();
+}
+
+static Status reduce_fused_segments(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
+                                    MsmWork& wk, hipStream_t st) {
+    EON_TRY(begin_segments(ctx, bt, wk, st));
+    hipLaunchKernelGGL(k_segment_reduce29, dim3(blocks_for((uint64_t)bt.B / SEG * bt.groups, 64)), dim3(64), 0, st,
+                       wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, bt.groups, wk.red_a.as<G1Xyzz>());
+    return tree_sum_segments(ctx, L, bt, wk, st);
+}
+
+static Status reduce_combine_segments(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
+                                      MsmWork& wk, hipStream_t st) {
+    EON_TRY(combine_levels(ctx, bt, sr, wk, st));
+    EON_TRY(begin_segments(ctx, bt, wk, st));
+    hipLaunchKernelGGL(k_segment_sum, dim3(blocks_for((uint64_t)bt.B / SEG * bt.groups, 64)), dim3(64), 0, st,
+                       wk.bucket_sums.as<G1Xyzz>(), bt.B, bt.groups, wk.red_a.as<G1Xyzz>());
+    return tree_sum_segments(ctx, L, bt, wk, st);
+}
+
+static Status reduce_sums29(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr, MsmWork& wk,
+                            hipStream_t st) {
+    const uint32_t groups = bt.groups;
+    ctx->prof.begin("k_bucket_sums29", (uint64_t)bt.n_pieces * 144 + (uint64_t)bt.nb * 144, st);
+    hipLaunchKernelGGL(k_bucket_sums29, dim3(blocks_for(bt.nb, 256)), dim3(256), 0, st, wk.piece_raw.as<G1Raw29>(),
+                       sr.piece_off, bt.B, groups, wk.piece_sums.as<G1Raw29>());
+    ctx->prof.end(st);
+    EON_HIP(hipGetLastError());
+    EON_TRY(begin_segments(ctx, bt, wk, st));
+    // raw bucket sums (k_bucket_sums29, in wk.piece_sums as G1Raw29) -> one raw partial per
+    // 256 segments -> one point per group, all in radix 2^29
+    const uint32_t seg = std::min(bt.B, seg29_for((uint64_t)bt.B * groups));
+    const uint32_t bpg = (bt.B / seg + SEG_BLOCK - 1) / SEG_BLOCK;
+    EON_HIP(ctx_ensure(ctx, wk.red_b, (uint64_t)groups * bpg * sizeof(G1Raw29)));
+    hipLaunchKernelGGL(k_segment_sum29, dim3(groups * bpg), dim3(SEG_BLOCK), 0, st, wk.piece_sums.as<G1Raw29>(),
+                       bt.B, seg, bpg, wk.red_b.as<G1Raw29>());
+    hipLaunchKernelGGL(k_tree_sum29, dim3(groups), dim3(SEG_BLOCK), 0, st, wk.red_b.as<G1Raw29>(), bpg,
+                       wk.red_a.as<G1Xyzz>());
+    ctx->prof.end(st);
+    EON_HIP(hipGetLastError());
+    return write_columns(L, bt, wk.red_a.as<G1Xyzz>(), st);
+}
+
+// the batch's first-level segment sums into its rows of the call-wide arrays (DeferredFinish)
+static Status reduce_deferred(eon_ctx* ctx, const Batch& bt, const SortedRef& sr, MsmWork& wk, hipStream_t st,
+                              DeferredFinish& df) {
+    const uint64_t row0 = (uint64_t)(bt.out - df.out_base);
+    EON_TRY(piece_merge(ctx, bt, sr, wk, st));
+    ctx->prof.begin("bucket_reduce", (uint64_t)bt.nb * 128 + (uint64_t)bt.nb / SEG * 256, st);
+    hipLaunchKernelGGL(k_bucket_reduce29<G1Raw29>, dim3(blocks_for((uint64_t)df.nseg * bt.groups, 64)), dim3(64), 0,
+                       st, wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, RED_SEG, bt.groups, df.T + row0 * df.nseg,
+                       df.U + row0 * df.nseg);
+    ctx->prof.end(st);
+    EON_HIP(hipGetLastError());
+    df.rows.emplace_back(row0, bt.groups);
+    return Status::ok();
+}
+
+// sum_d d * B_d per group (bucket b holds digit b + 1): segment sums T, U of SEG buckets
+// (k_bucket_reduce29 from the raw pieces, or k_seg_level from bucket sums), then k_group_finish
+struct GroupLevel {
+    G1Xyzz *T, *U;
+    uint32_t seg, nseg;
+};
+
+// the group routes open alike: the per-group buffer and the bucket_reduce record
+static Status begin_groups(eon_ctx* ctx, const Batch& bt, MsmWork& wk, hipStream_t st, GroupLevel& g) {
+    g.T = wk.piece_sums.as<G1Xyzz>();
+    g.U = wk.piece_sums2.as<G1Xyzz>();
+    EON_HIP(wk.red_a.ensure((uint64_t)bt.groups * sizeof(G1Xyzz)));
+    ctx->prof.begin("bucket_reduce", (uint64_t)bt.nb * 128 + (uint64_t)bt.nb / SEG * 256, st);
+    g.seg = bt.B < SEG ? bt.B : SEG;
+    g.nseg = bt.B / g.seg;
+    return Status::ok();
+}
+
+// k_group_finish over the segment sums (closing the bucket_reduce record), then the columns
+static Status finish_groups(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const GroupLevel& g, MsmWork& wk,
+                            hipStream_t st) {
     G1Xyzz* per_group = wk.red_a.as<G1Xyzz>();
-    hipLaunchKernelGGL(k_group_finish<FINISH_THREADS>, dim3(groups), dim3(FINISH_THREADS), 0, st, T, u_buf, nseg,
-                       31 - __builtin_clz(seg), per_group);
-    prof->end(st);
+    hipLaunchKernelGGL(k_group_finish<FINISH_THREADS>, dim3(bt.groups), dim3(FINISH_THREADS), 0, st, g.T, g.U, g.nseg,
+                       31 - __builtin_clz(g.seg), per_group);
+    ctx->prof.end(st);
     EON_HIP(hipGetLastError());
     return write_columns(L, bt, per_group, st);
 }
 
-static hipError_t launch_group_finish29(const G1Raw29* T, const G1Raw29* U, uint32_t nseg, uint32_t lsg,
-                                        G1Xyzz* out, uint32_t groups, hipStream_t st) {
-    hipLaunchKernelGGL(k_group_finish29<FINISH_THREADS>, dim3(groups), dim3(FINISH_THREADS), 0, st, T, U, nseg, lsg,
-                       out);
-    return hipGetLastError();
+static Status reduce_fused_groups(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
+                                  MsmWork& wk, hipStream_t st) {
+    GroupLevel g;
+    EON_TRY(begin_groups(ctx, bt, wk, st, g));
+    EON_TRY(piece_merge(ctx, bt, sr, wk, st));
+    hipLaunchKernelGGL(k_bucket_reduce29<G1Xyzz>, dim3(blocks_for((uint64_t)g.nseg * bt.groups, 64)), dim3(64), 0, st,
+                       wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, g.seg, bt.groups, g.T, g.U);
+    return finish_groups(ctx, L, bt, g, wk, st);
+}
+
+static Status reduce_combine_groups(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
+                                    MsmWork& wk, hipStream_t st) {
+    EON_TRY(combine_levels(ctx, bt, sr, wk, st));
+    GroupLevel g;
+    EON_TRY(begin_groups(ctx, bt, wk, st, g));
+    hipLaunchKernelGGL(k_seg_level, dim3(blocks_for((uint64_t)g.nseg * bt.groups, 64)), dim3(64), 0, st,
+                       wk.bucket_sums.as<G1Xyzz>(), bt.B, g.seg, bt.groups, g.T, g.U);
+    return finish_groups(ctx, L, bt, g, wk, st);
+}
+
+// combine levels, bucket sums and the weighted bucket reduction of one batch's pieces by the
+// batch's route (reduce_route; no read-backs: the counts came with batch_counts); leaves one XYZZ
+// point per column at bt.out, or, deferred, the group's segment sums in df's rows.  The
+// sorted piece offsets are only read (a prepared batch is reduced once per bases object).
+static Status batch_reduce(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, const SortedRef& sr,
+                           MsmWork& wk, hipStream_t st, DeferredFinish& df) {
+    switch (reduce_route(bt, L, df.T != nullptr)) {
+        case Reduce::Deferred: return reduce_deferred(ctx, bt, sr, wk, st, df);
+        case Reduce::FusedGroups: return reduce_fused_groups(ctx, L, bt, sr, wk, st);
+        case Reduce::FusedSegments: return reduce_fused_segments(ctx, L, bt, sr, wk, st);
+        case Reduce::Sums29: return reduce_sums29(ctx, L, bt, sr, wk, st);
+        case Reduce::CombineGroups: return reduce_combine_groups(ctx, L, bt, sr, wk, st);
+        case Reduce::CombineSegments: return reduce_combine_segments(ctx, L, bt, sr, wk, st);
+    }
+    return Status::err(EON_E_ARG, "unknown bucket reduction route");
 }
 
 }  // namespace eon
@@ -2044,7 +1971,7 @@ Status msm_run_columns(eon_ctx* ctx, const eon_msm_bases* b, const Fr* scalars, 
     auto pieces = [&](size_t k) -> Status {
         const int i = (int)(k & 1), w = (int)(k % 3);
         EON_HIP(hipStreamWaitEvent(comp[i], ctx->msm_sorted[w], 0));
-        return batch_pieces(ctx, b, batches[k], sorted_ref(sorted_of(k)), *wks[w], comp[i]);
+        return batch_pieces(ctx, L, b, batches[k], sorted_ref(sorted_of(k)), *wks[w], comp[i]);
     };
     DeferredFinish df;
     EON_TRY(prepare_deferred(ctx, L, width, res_xyzz, df));
@@ -2055,8 +1982,7 @@ Status msm_run_columns(eon_ctx* ctx, const eon_msm_bases* b, const Fr* scalars, 
         // the latency-bound reduction (measured +20 ms per prove)
         EON_TRY(pieces(k));
         if (k + 1 < batches.size()) EON_TRY(sort_batch(k + 1, true));
-        EON_TRY(batch_reduce(ctx, L, batches[k], sorted_ref(sorted_of(k)), *wks[w], comp[i],
-                             fused_reduce(batches[k]), &df));
+        EON_TRY(batch_reduce(ctx, L, batches[k], sorted_ref(sorted_of(k)), *wks[w], comp[i], df));
         EON_HIP(hipEventRecord(ctx->msm_reduced[w], comp[i]));
     }
     // the context stream resumes after both compute streams' last reductions
@@ -2070,7 +1996,6 @@ Status msm_run_columns(eon_ctx* ctx, const eon_msm_bases* b, const Fr* scalars, 
         keep->batches = batches;
         for (Batch& bt : keep->batches) bt.scalars = nullptr;
     }
-    (void)res;
     if (out_host) return results_to_host_affine(res_xyzz, width, out_host, ctx->stream);
     EON_HIP(hipStreamSynchronize(ctx->stream));
     return Status::ok();
@@ -2114,15 +2039,14 @@ Status msm_run_prepared(eon_ctx* ctx, const eon_msm_bases* const* bases, uint32_
             Batch bt = s->batches[k];
             bt.out = res_xyzz + (uint64_t)t * width + bt.col0;
             const SortedRef sr = sorted_ref(s->sorted[k]);
-            EON_TRY(batch_pieces(ctx, bases[t], bt, sr, *wks[j % NS], st));
-            EON_TRY(batch_reduce(ctx, s->layout, bt, sr, *wks[j % NS], st, fused_reduce(bt), &df));
+            EON_TRY(batch_pieces(ctx, s->layout, bases[t], bt, sr, *wks[j % NS], st));
+            EON_TRY(batch_reduce(ctx, s->layout, bt, sr, *wks[j % NS], st, df));
         }
     for (uint32_t i = 1; i < NS; i++) {
         EON_HIP(hipEventRecord(ctx->msm_ev[1], comp[i]));
         EON_HIP(hipStreamWaitEvent(ctx->stream, ctx->msm_ev[1], 0));
     }
     EON_TRY(run_deferred_finish(ctx, df, ctx->stream));
-    (void)res;
     return results_to_host_affine(res_xyzz, total, out_host, ctx->stream);
 }
 

@@ -288,6 +288,76 @@ def test_columns_piece_merge(gpu_ctx, rows, cancel):
         assert as_py(got[j]) == (O.g1_mul(P, k) if k else O.INF), j
 
 
+def _route_deferred():
+    return True, C.random_fr(51, 256 * 66).reshape(256, 66, 4)
+
+
+def _route_fused_groups():
+    return False, C.random_fr(52, 300 * 3).reshape(300, 3, 4)
+
+
+def _route_fused_segments():
+    return False, C.random_fr(53, 160)
+
+
+def _route_sums29():
+    return True, C.random_fr(54, 200 * 7).reshape(200, 7, 4)
+
+
+def _route_combine_segments():
+    return True, np.repeat(C.random_fr(55, 1), 1024, axis=0)
+
+
+def _route_combine_groups():
+    mat = C.random_fr(56, 256 * 66).reshape(256, 66, 4)
+    mat[:, 0] = fr(int.from_bytes(b"\x01" * 32, "little"))
+    return True, mat
+
+
+# route: (inputs, profiler records that must be present, records that must be absent)
+REDUCE_ROUTES = {
+    "Deferred": (_route_deferred, {"bucket_reduce", "k_group_finish"}, {"k_partial_combine"}),
+    "FusedGroups": (_route_fused_groups, {"bucket_reduce"}, {"k_group_finish", "k_partial_combine"}),
+    "FusedSegments": (_route_fused_segments, {"k_segment_sum"}, {"k_bucket_sums29", "k_partial_combine"}),
+    "Sums29": (_route_sums29, {"k_bucket_sums29", "k_segment_sum"}, set()),
+    "CombineSegments": (_route_combine_segments, {"k_partial_combine", "k_segment_sum"}, set()),
+    "CombineGroups": (_route_combine_groups, {"k_partial_combine", "bucket_reduce"}, {"k_group_finish"}),
+}
+
+
+@pytest.mark.parametrize("route", list(REDUCE_ROUTES))
+def test_reduce_routes(gpu_ctx, monkeypatch, route):
+    """The six routes of the bucket reduction (reduce_route, msm.hip), each at the smallest shape
+    that reaches it and named by the profiler records it leaves:
+    Deferred         fixed-base, 66 columns x 256 rows (c = 8, B = 128): >= 64 groups, one finish
+                     launch per call;
+    FusedGroups      plain bases, 3 columns x 300 rows (c = 5, 153 groups): the per-batch finish
+                     runs inside the bucket_reduce record;
+    FusedSegments    plain bases, one MSM of 160 scalars (c = 5, 51 groups, pieces <= 2 nb);
+    Sums29           fixed-base, 7 columns x 200 rows (c = 8, pieces > 2 nb);
+    CombineSegments  fixed-base, one MSM of 1024 equal scalars: 64 pieces in one bucket;
+    CombineGroups    fixed-base, 66 columns x 256 rows, column 0 the scalar 0x0101...01 in every
+                     row: all 32 windows of the column land in one bucket (512 pieces).
+    Every column equals the C Pippenger restatement's."""
+    monkeypatch.delenv("EON_MSM_FORCE_C", raising=False)
+    make, present, absent = REDUCE_ROUTES[route]
+    precompute, s = make()
+    pts = srs_powers(s.shape[0], 12345, gpu_ctx)
+    bases = MsmBases(pts, gpu_ctx, precompute=precompute)
+    gpu_ctx.profile(True)
+    try:
+        got = bases.msm(s) if s.ndim == 2 else bases.msm_columns(s)
+        kernels = set(gpu_ctx.profile_report())
+    finally:
+        gpu_ctx.profile(False)
+    assert present <= kernels and not (absent & kernels), sorted(kernels)
+    if s.ndim == 2:
+        np.testing.assert_array_equal(got, C.g1_msm(pts, s))
+    else:
+        for j in range(s.shape[1]):
+            np.testing.assert_array_equal(got[j], C.g1_msm(pts, s[:, j]), err_msg=f"column {j}")
+
+
 def test_all_windows_knob_same_result():
     """EON_MSM_ALL_WINDOWS=1 (digitise every window, not only those the largest scalar reaches)
     gives the same MSMs: window-boundary scalars and full-range ones, in a fresh process (the knob
