@@ -238,6 +238,15 @@ int eon_diag_msm_scalars_batches(eon_ctx* ctx, const eon_msm_scalars* prepared, 
  * Reads only; the handle is unchanged. */
 int eon_diag_msm_scalars_batch(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t k, eon_msm_batch_info* info,
                                uint32_t* keys, uint32_t* vals, uint32_t* start, uint32_t* piece_off);
+/* Batch k's bucket order, kept by column batches (>= 64 groups) for the one-bucket-per-lane piece
+ * sums: per window of *window consecutive bucket indices (the last may be short), those indices
+ * stably sorted by run length start[b + 1] - start[b], shortest first (lengths of 1023 and above
+ * compare equal).  *window = 0 for a batch without an order, whose `order` is then left unwritten;
+ * otherwise `order`, when not NULL, receives info->nb entries.  *bucket_lanes = 1 when the batch's
+ * piece sums take the one-bucket-per-lane route (every MSM against the handle does alike), 0 for
+ * the chunked route.  Reads only. */
+int eon_diag_msm_scalars_order(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t k, uint32_t* window,
+                               uint32_t* bucket_lanes, uint32_t* order);
 
 /* One single-column MSM over device scalars as eon_msm_g1_dev runs it -- digitising only the
  * windows its largest scalar reaches (one more for the recoding's carry), which a handle made by
@@ -248,6 +257,7 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   15: eon_diag_msm_scalars_order, a column batch's bucket order and piece-sum route, additive;
  *   14: eon_g1_compress[_dev], the inverse of eon_g1_decompress[_dev], and EON_E_FORMAT, additive;
  *   13: eon_fr_fold_columns_dev, the gamma-fold of the batched KZG opening, additive;
  *   12: loading a supplied SRS -- eon_g1_decompress[_dev], eon_g1_validate_dev, eon_kzg_srs_check,

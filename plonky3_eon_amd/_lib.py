@@ -34,7 +34,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 14  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 15  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -137,6 +137,7 @@ SIGNATURES = {
     "eon_diag_msm_g1_prepare_active_dev": (_INT, [_P, _P, _P, _U64, _P, ctypes.POINTER(_P)]),
     "eon_diag_msm_scalars_batches": (_INT, [_P, _P, _P]),
     "eon_diag_msm_scalars_batch": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _P]),
+    "eon_diag_msm_scalars_order": (_INT, [_P, _P, _U32, _P, _P, _P]),
     "eon_ctx_profile": (_INT, [_P, _INT]),
     "eon_ctx_profile_report": (_INT, [_P, ctypes.c_char_p, _U64]),
     "eon_ctx_set_serial": (_INT, [_P, _INT]),

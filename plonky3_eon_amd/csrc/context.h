@@ -129,12 +129,14 @@ struct Status {
 // of the same scalars against other bases).
 struct SortedBufs {
     DevBuf keys2, vals2, start, piece_off;
-    size_t bytes() const { return keys2.bytes + vals2.bytes + start.bytes + piece_off.bytes; }
+    DevBuf order;  // column batches: the buckets by run length per window (k_bucket_order, msm.hip)
+    size_t bytes() const { return keys2.bytes + vals2.bytes + start.bytes + piece_off.bytes + order.bytes; }
     void release() {
         keys2.release();
         vals2.release();
         start.release();
         piece_off.release();
+        order.release();
     }
 };
 

@@ -16,7 +16,9 @@
 //                       sorted pairs); exclusive scan of the per-bucket piece counts.
 //   5. k_piece_sum29    one thread per chunk of sorted pairs (every lane does the same number of
 //                       XYZZ mixed additions of affine bases, radix 2^29), flushing a partial per
-//                       piece.
+//                       piece.  Column batches (>= 64 groups, no skew) instead give every lane one
+//                       whole bucket, 64 buckets of nearly equal length per wave
+//                       (k_bucket_order at sort time, k_piece_sum_bucket29): one piece per bucket.
 //   6. k_partial_combine levels of <= PIECE-way sums until each bucket holds one partial
 //                       (log-depth under any skew, e.g. all-equal scalars), k_bucket_final.
 //   7. k_bucket_reduce29 sum_d d * B_d per group: T_j / U_j the plain / locally weighted sums of
@@ -375,6 +377,82 @@ __global__ void __launch_bounds__(256) k_bucket_start(const uint32_t* keys, uint
     }
 }
 
+// Bucket order of the one-bucket-per-lane piece sums (k_piece_sum_bucket29): per window of
+// ORDER_WINDOW consecutive bucket indices, the indices stably sorted by run length
+// start[b + 1] - start[b], shortest first, so that 64 consecutive entries -- one wave -- hold runs of
+// nearly equal length (uniform scalars: 0.999 of the lane slots busy against 0.766 in index order).
+// One block per window, a counting sort: an LDS histogram of the lengths (those above ORDER_CAP
+// share the last bin, in index order), its scan, then tiles of ORDER_THREADS buckets in index order,
+// each lane ranked among the equal lengths of its wave by ballots and each wave behind the earlier
+// waves of its tile.  The batch's longest run goes to *max_run (zeroed by the caller).
+// The window keeps a wave's 64 runs inside the pairs of 2^15 neighbouring buckets (~8 MB of `vals`
+// at the prove's 64 pairs per bucket): sorting the whole batch instead would spread them over all
+// of it for no utilisation left to gain.
+constexpr uint32_t ORDER_WINDOW = 1u << 15;
+constexpr uint32_t ORDER_THREADS = 512, ORDER_WAVES = ORDER_THREADS / 64;
+constexpr uint32_t ORDER_BIN_BITS = 10;
+constexpr uint32_t ORDER_BINS = 1u << ORDER_BIN_BITS, ORDER_CAP = ORDER_BINS - 1;
+__global__ void __launch_bounds__(ORDER_THREADS) k_bucket_order(const uint32_t* start, uint32_t nb, uint32_t* order,
+                                                                uint32_t* max_run) {
+    __shared__ uint32_t base[ORDER_BINS];                  // next free slot of every length
+    __shared__ uint32_t wave_cnt[ORDER_WAVES][ORDER_BINS];  // the tile's buckets per wave and length
+    __shared__ uint32_t longest;
+    const uint32_t b0 = blockIdx.x * ORDER_WINDOW;
+    const uint32_t b1 = min(b0 + ORDER_WINDOW, nb);
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    for (uint32_t i = tid; i < ORDER_BINS; i += ORDER_THREADS) base[i] = 0;
+    if (tid == 0) longest = 0;
+    __syncthreads();
+    uint32_t mx = 0;
+    for (uint32_t b = b0 + tid; b < b1; b += ORDER_THREADS) {
+        const uint32_t len = start[b + 1] - start[b];
+        mx = max(mx, len);
+        atomicAdd(&base[min(len, ORDER_CAP)], 1u);
+    }
+    atomicMax(&longest, mx);
+    __syncthreads();
+    if (tid == 0) {
+        if (longest) atomicMax(max_run, longest);
+        uint32_t sum = 0;
+        for (uint32_t i = 0; i < ORDER_BINS; i++) {
+            const uint32_t n = base[i];
+            base[i] = sum;
+            sum += n;
+        }
+    }
+    for (uint32_t t0 = b0; t0 < b1; t0 += ORDER_THREADS) {
+        for (uint32_t i = tid; i < ORDER_WAVES * ORDER_BINS; i += ORDER_THREADS) (&wave_cnt[0][0])[i] = 0;
+        __syncthreads();  // also orders the scan of `base` before the first tile
+        const uint32_t b = t0 + tid;
+        const bool live = b < b1;
+        const uint32_t bin = live ? min(start[b + 1] - start[b], ORDER_CAP) : 0u;
+        // the lanes of this wave with the same length: one ballot per bin bit
+        uint64_t same = __ballot(live);
+#pragma unroll
+        for (uint32_t k = 0; k < ORDER_BIN_BITS; k++) {
+            const uint64_t m = __ballot((bin >> k) & 1u);
+            same &= ((bin >> k) & 1u) ? m : ~m;
+        }
+        const uint32_t rank = __popcll(same & ((1ull << lane) - 1));
+        if (live && rank == 0) wave_cnt[wave][bin] = __popcll(same);
+        __syncthreads();
+        for (uint32_t i = tid; i < ORDER_BINS; i += ORDER_THREADS) {
+            // counts -> slots: the earlier waves' buckets of this length first
+            uint32_t at = base[i];
+#pragma unroll
+            for (uint32_t w = 0; w < ORDER_WAVES; w++) {
+                const uint32_t n = wave_cnt[w][i];
+                wave_cnt[w][i] = at;
+                at += n;
+            }
+            base[i] = at;
+        }
+        __syncthreads();
+        if (live) order[b0 + wave_cnt[wave][bin] + rank] = b;
+        __syncthreads();
+    }
+}
+
 __global__ void k_piece_owner(const uint32_t* piece_off, uint32_t nb, uint32_t* owner) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb) return;
@@ -530,6 +608,81 @@ __global__ void __launch_bounds__(64, PIECE_MINWAVES) k_piece_sum29(
     }
 }
 
+// The piece sums of a column batch, one whole bucket per lane: the wave takes 64 consecutive entries
+// of `order` (k_bucket_order: runs of nearly equal length), lane l sums the pairs
+// [start[b], start[b + 1]) of its bucket b and stores the bucket's one piece at index b.  Every lane
+// opens its run in the first iteration and flushes after the last, so the wave executes the run
+// start and the flush once instead of wherever one of 64 chunks crosses a bucket boundary, no
+// bucket is cut in two (nothing to merge) and the keys are not read.  The arithmetic is
+// k_piece_sum29's.  Correct for any run lengths; the host sends skewed batches down the chunked
+// route because a wave here runs as long as its longest bucket.
+__global__ void __launch_bounds__(64, PIECE_MINWAVES) k_piece_sum_bucket29(
+    const uint32_t* vals, const uint32_t* start, const uint32_t* order, uint32_t nb, bool vec,
+    const G1Affine* pts29, G1Raw29* piece_raw) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < nb;
+    const uint32_t b = live ? order[i] : 0u;
+    const uint32_t e0 = live ? start[b] : 0u;
+    const uint32_t len = live ? start[b + 1] - e0 : 0u;
+    // the wave's longest run bounds the loop (a uniform trip count); shorter runs sit out the rest
+    uint32_t longest = len;
+#pragma unroll
+    for (uint32_t d = 32; d >= 1; d >>= 1) longest = max(longest, (uint32_t)__shfl_xor((int)longest, (int)d));
+    longest = __builtin_amdgcn_readfirstlane(longest);
+    G1X29 acc;
+    bool inf = true;
+    // the accumulator holds (-1)^flip times the run's sum, as in k_piece_sum29
+    bool flip = false;
+    // the references in aligned 16-byte quads with a per-lane pick: a lane's run starts at any pair,
+    // so its first quad is aligned down (the pairs before the run are loaded and not picked) and
+    // the lanes reload at different iterations; prove -0.7 % A/B against one 4-byte load per pair
+    // fetched an iteration ahead.  vec: the batch holds a multiple of 4 pairs, so the last quad
+    // stays inside `vals`; otherwise one pair at a time into component 0.
+    uint4 vq = make_uint4(0, 0, 0, 0);
+    for (uint32_t k = 0; k < longest; k++) {
+        if (k >= len) continue;
+        const uint32_t e = e0 + k, sub = vec ? (e & 3u) : 0u;
+        if (vec) {
+            if (k == 0 || sub == 0) vq = *reinterpret_cast<const uint4*>(vals + (e & ~3u));
+        } else {
+            vq.x = vals[e];
+        }
+        const uint32_t v = sub == 0 ? vq.x : sub == 1 ? vq.y : sub == 2 ? vq.z : vq.w;
+        G1Affine a = ld_affine(pts29 + (v & 0x7fffffffu));
+        if (a.y.is_zero()) continue;
+        const bool neg_digit = v >> 31;
+        const F29 ax = unpack29(a.x), ay = unpack29(a.y);
+        if (inf) {
+            acc.X = ax;
+            acc.Y = ay;
+            acc.ZZ = const29<FqP>(R29<FqP>::ONE);
+            acc.ZZZ = acc.ZZ;
+            flip = neg_digit;
+            inf = false;
+        } else {
+            const F29 ayn = neg29_lazy<2>(ay);
+            const bool ng = neg_digit != flip;
+            F29 ys;
+#pragma unroll
+            for (int j = 0; j < 9; j++) ys.l[j] = ng ? ayn.l[j] : ay.l[j];
+            madd29_negsum(acc, ax, ys);
+            flip = !flip;
+        }
+    }
+    if (!live) return;
+    // the one flush: a run that met an exceptional addition (ZZ = 0 mod p) is summed again, checked
+    if (!inf && is_zero_mod29<FqP>(acc.ZZ)) {
+        inf = piece_run29(vals, pts29, e0, e0 + len, acc);
+        flip = false;
+    }
+    if (inf) {  // an empty bucket, identity bases only, or a sum that cancelled
+        st_raw29_inf(piece_raw + b);
+        return;
+    }
+    if (flip) acc.ZZZ = neg29_lazy<3>(acc.ZZZ);  // ZZZ < 2p normalised -> 3p - ZZZ
+    st_raw29(piece_raw + b, acc);
+}
+
 __global__ void k_raw29_to_xyzz(const G1Raw29* in, uint32_t n, G1Xyzz* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -666,7 +819,8 @@ __global__ void __launch_bounds__(64) k_piece_merge29(const uint32_t* keys, cons
         st_raw29(pieces + p0, a);
 }
 
-template <class OutT>
+// ONE_PIECE: the pieces of k_piece_sum_bucket29, bucket bp's one piece at index bp (piece_off unread)
+template <class OutT, bool ONE_PIECE>
 __global__ void __launch_bounds__(64) k_bucket_reduce29(const G1Raw29* pieces, const uint32_t* piece_off,
                                                         uint32_t B, uint32_t seg, uint32_t groups, OutT* T,
                                                         OutT* U) {
@@ -678,8 +832,8 @@ __global__ void __launch_bounds__(64) k_bucket_reduce29(const G1Raw29* pieces, c
     bool run_inf = true, acc_inf = true;
     for (int k = (int)seg - 1; k >= 0; k--) {
         const uint32_t bp = (s * seg + (uint32_t)k) * groups + g;
-        const uint32_t e0 = piece_off[bp];
-        uint32_t e1 = piece_off[bp + 1];
+        const uint32_t e0 = ONE_PIECE ? bp : piece_off[bp];
+        uint32_t e1 = ONE_PIECE ? bp + 1 : piece_off[bp + 1];
         if (e1 - e0 == 2) e1 = e0 + 1;  // k_piece_merge29 summed the two into the first
         for (uint32_t e = e0; e < e1; e++) {
             const bool inf = ld_raw29(pieces + e, x);
@@ -1152,10 +1306,14 @@ struct Batch {
     bool counted = false;  // n_pieces / n_pairs / levels read back (batch_counts)
     size_t prof_rec = SIZE_MAX;  // the k_piece_sum profiler record to complete with the counts
     uint32_t w_act = 0;   // windows that can hold a nonzero digit (0: all of the layout's)
+    bool ordered = false;   // the sorted buffers hold the batch's bucket order (k_bucket_order)
+    uint32_t max_run = 0;   // ordered and counted: the pairs of the batch's largest bucket
+    bool bucket_lanes = false;  // the pieces are k_piece_sum_bucket29's (set by batch_pieces)
 };
 
 struct SortedRef {
     const uint32_t *keys, *vals, *start, *piece_off;
+    const uint32_t* order;  // meaningful for an ordered batch (Batch::ordered)
 };
 
 static bool msm_debug() {
@@ -1304,13 +1462,24 @@ static Status batch_sort(eon_ctx* ctx, const MsmLayout& L, uint64_t n, uint64_t 
     EON_HIP(hipMemsetAsync(wk.stat.p, 0, 16, st));
     EON_HIP(exclusive_scan_chunk_counts(wk.temp.p, out.start.as<uint32_t>(), nb, bt.log_chunk,
                                         out.piece_off.as<uint32_t>(), wk.stat.as<uint32_t>(), st));
+    // column batches: the bucket order of the one-bucket-per-lane piece sums, and the longest run
+    // (wk.stat[1]) for the route choice (bucket_lanes_route)
+    bt.ordered = bt.groups >= 64;
+    if (bt.ordered) {
+        EON_HIP(ctx_ensure(ctx, out.order, (uint64_t)nb * 4));
+        prof->begin("k_bucket_order", (uint64_t)nb * 12, st);
+        hipLaunchKernelGGL(k_bucket_order, dim3(blocks_for(nb, ORDER_WINDOW)), dim3(ORDER_THREADS), 0, st,
+                           out.start.as<uint32_t>(), nb, out.order.as<uint32_t>(), wk.stat.as<uint32_t>() + 1);
+        prof->end(st);
+        EON_HIP(hipGetLastError());
+    }
     // the sorted pairs are ready for the piece sums (sorted_ev), ahead of the count read-back
     EON_HIP(hipEventRecord(sorted_ev, st));
     // the reduction's launches are sized by the real counts (12-byte read-back: pieces, nonzero
     // digits, max pieces); batch_counts waits for them
     EON_HIP(hipMemcpyAsync(wk.host_counts, out.piece_off.as<uint32_t>() + nb, 4, hipMemcpyDeviceToHost, st));
     EON_HIP(hipMemcpyAsync(wk.host_counts + 1, out.start.as<uint32_t>() + nb, 4, hipMemcpyDeviceToHost, st));
-    EON_HIP(hipMemcpyAsync(wk.host_counts + 3, wk.stat.p, 4, hipMemcpyDeviceToHost, st));
+    EON_HIP(hipMemcpyAsync(wk.host_counts + 3, wk.stat.p, 8, hipMemcpyDeviceToHost, st));  // + the longest run
     if (!wk.counts_ev) EON_HIP(hipEventCreateWithFlags(&wk.counts_ev, hipEventDisableTiming));
     EON_HIP(hipEventRecord(wk.counts_ev, st));
     bt.counted = false;
@@ -1323,6 +1492,7 @@ static Status batch_counts(eon_ctx* ctx, Batch& bt, MsmWork& wk, uint64_t n) {
     bt.n_pairs = wk.host_counts[1];
     bt.levels = 0;
     for (uint64_t m = wk.host_counts[3]; m > 1; m = (m + PIECE - 1) / PIECE) bt.levels++;
+    bt.max_run = wk.host_counts[4];
     if (msm_debug())
         fprintf(stderr, "msm_batch n=%llu cols=%u c=%u W=%u nb=%u E=%llu pairs=%u pieces=%u\n",
                 (unsigned long long)n, bt.cols, bt.c, bt.W, bt.nb, (unsigned long long)bt.E, bt.n_pairs,
@@ -1338,7 +1508,7 @@ static Status batch_counts(eon_ctx* ctx, Batch& bt, MsmWork& wk, uint64_t n) {
 
 static SortedRef sorted_ref(const SortedBufs& s) {
     return SortedRef{s.keys2.as<uint32_t>(), s.vals2.as<uint32_t>(), s.start.as<uint32_t>(),
-                     s.piece_off.as<uint32_t>()};
+                     s.piece_off.as<uint32_t>(), s.order.as<uint32_t>()};
 }
 
 // The way a counted batch's pieces become one point per group (batch_reduce): the Fused routes and
@@ -1371,6 +1541,17 @@ static Reduce reduce_route(const Batch& bt, const MsmLayout& L, bool deferred_av
     return few_groups ? Reduce::CombineSegments : Reduce::CombineGroups;
 }
 
+// Whether a counted batch's piece sums run one bucket per lane (k_piece_sum_bucket29) instead of one
+// chunk per lane: a column batch (>= 64 groups, so it has its bucket order) whose reduction is the
+// one-level k_bucket_reduce29 and whose largest bucket is within ORDER_CAP pairs.  The cap is for
+// speed alone: a wave runs as long as its longest bucket, k_bucket_order sorts lengths only up to
+// the cap, and the chunked route bounds every lane's work whatever the skew.
+static bool bucket_lanes_route(const Batch& bt, const MsmLayout& L) {
+    if (!bt.counted || !bt.ordered || bt.groups < 64 || bt.max_run > ORDER_CAP) return false;
+    const Reduce r = reduce_route(bt, L, true);
+    return r == Reduce::Deferred || r == Reduce::FusedGroups;
+}
+
 // piece sums of one sorted batch against bases `b` (asynchronous); wk supplies the piece buffers
 static Status batch_pieces(eon_ctx* ctx, const MsmLayout& L, const eon_msm_bases* b, Batch& bt, const SortedRef& sr,
                            MsmWork& wk, hipStream_t st) {
@@ -1395,6 +1576,18 @@ static Status batch_pieces(eon_ctx* ctx, const MsmLayout& L, const eon_msm_bases
     // profiler record gets its counts later
     const uint64_t pairs_max = bt.counted ? bt.n_pairs : bt.E;
     if (!bt.counted && ctx->prof.enabled) bt.prof_rec = ctx->prof.recs.size();
+    bt.bucket_lanes = bucket_lanes_route(bt, L);
+    if (bt.bucket_lanes) {
+        // design bytes: a 4-byte reference and a 64-byte table entry per pair; per bucket its order
+        // entry, its two starts and one 144-byte piece
+        ctx->prof.begin("k_piece_sum", (uint64_t)bt.cols * msm_n * 96, st, (uint64_t)bt.n_pairs * 10,
+                        (uint64_t)bt.n_pairs * 68 + (uint64_t)bt.nb * 156);
+        hipLaunchKernelGGL(k_piece_sum_bucket29, dim3(blocks_for(bt.nb, 64)), dim3(64), 0, st, sr.vals, sr.start,
+                           sr.order, bt.nb, (bt.E & 3) == 0, pts, wk.piece_raw.as<G1Raw29>());
+        ctx->prof.end(st);
+        EON_HIP(hipGetLastError());
+        return Status::ok();
+    }
     ctx->prof.begin("k_piece_sum", (uint64_t)bt.cols * msm_n * 96, st, (uint64_t)bt.n_pairs * 10,
                     (uint64_t)bt.n_pairs * 72 + (uint64_t)bt.n_pieces * 144);
     const uint32_t blocks = blocks_for((pairs_max + (1u << bt.log_chunk) - 1) >> bt.log_chunk, 64);
@@ -1602,10 +1795,11 @@ static Status reduce_sums29(eon_ctx* ctx, const MsmLayout& L, const Batch& bt, c
 static Status reduce_deferred(eon_ctx* ctx, const Batch& bt, const SortedRef& sr, MsmWork& wk, hipStream_t st,
                               DeferredFinish& df) {
     const uint64_t row0 = (uint64_t)(bt.out - df.out_base);
-    EON_TRY(piece_merge(ctx, bt, sr, wk, st));
+    if (!bt.bucket_lanes) EON_TRY(piece_merge(ctx, bt, sr, wk, st));
     ctx->prof.begin("bucket_reduce", (uint64_t)bt.nb * 128 + (uint64_t)bt.nb / SEG * 256, st);
-    hipLaunchKernelGGL(k_bucket_reduce29<G1Raw29>, dim3(blocks_for((uint64_t)df.nseg * bt.groups, 64)), dim3(64), 0,
-                       st, wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, RED_SEG, bt.groups, df.T + row0 * df.nseg,
+    hipLaunchKernelGGL((bt.bucket_lanes ? k_bucket_reduce29<G1Raw29, true> : k_bucket_reduce29<G1Raw29, false>),
+                       dim3(blocks_for((uint64_t)df.nseg * bt.groups, 64)), dim3(64), 0, st,
+                       wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, RED_SEG, bt.groups, df.T + row0 * df.nseg,
                        df.U + row0 * df.nseg);
     ctx->prof.end(st);
     EON_HIP(hipGetLastError());
@@ -1646,8 +1840,9 @@ static Status reduce_fused_groups(eon_ctx* ctx, const MsmLayout& L, const Batch&
                                   MsmWork& wk, hipStream_t st) {
     GroupLevel g;
     EON_TRY(begin_groups(ctx, bt, wk, st, g));
-    EON_TRY(piece_merge(ctx, bt, sr, wk, st));
-    hipLaunchKernelGGL(k_bucket_reduce29<G1Xyzz>, dim3(blocks_for((uint64_t)g.nseg * bt.groups, 64)), dim3(64), 0, st,
+    if (!bt.bucket_lanes) EON_TRY(piece_merge(ctx, bt, sr, wk, st));
+    hipLaunchKernelGGL((bt.bucket_lanes ? k_bucket_reduce29<G1Xyzz, true> : k_bucket_reduce29<G1Xyzz, false>),
+                       dim3(blocks_for((uint64_t)g.nseg * bt.groups, 64)), dim3(64), 0, st,
                        wk.piece_raw.as<G1Raw29>(), sr.piece_off, bt.B, g.seg, bt.groups, g.T, g.U);
     return finish_groups(ctx, L, bt, g, wk, st);
 }
@@ -1975,7 +2170,9 @@ Status msm_run_columns(eon_ctx* ctx, const eon_msm_bases* b, const Fr* scalars, 
     };
     DeferredFinish df;
     EON_TRY(prepare_deferred(ctx, L, width, res_xyzz, df));
-    EON_TRY(sort_batch(0, false));
+    // a column batch's route needs its counts (bucket_lanes_route), so the first waits for them as
+    // the later ones do; a single MSM keeps launching its piece sums ahead of the read-back
+    EON_TRY(sort_batch(0, L.precomputed ? batches[0].cols >= 64 : (uint64_t)batches[0].cols * L.W >= 64));
     for (size_t k = 0; k < batches.size(); k++) {
         const int i = (int)(k & 1), w = (int)(k % 3);
         // pieces(k + 1) is enqueued only after reduce(k)'s read-backs: launched earlier it starves
@@ -2254,6 +2451,31 @@ int eon_diag_msm_scalars_batch(eon_ctx* ctx, const eon_msm_scalars* prepared, ui
         if (start) EON_HIP(hipMemcpyAsync(start, sb.start.p, bucket_bytes, hipMemcpyDeviceToHost, ctx->stream));
         if (piece_off)
             EON_HIP(hipMemcpyAsync(piece_off, sb.piece_off.p, bucket_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+int eon_diag_msm_scalars_order(eon_ctx* ctx, const eon_msm_scalars* prepared, uint32_t k, uint32_t* window,
+                               uint32_t* bucket_lanes, uint32_t* order) {
+    if (!ctx) return EON_E_ARG;
+    if (!prepared || !window || !bucket_lanes) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (prepared->ctx && prepared->ctx != ctx) return Status::err(EON_E_ARG, "prepared scalars of another context");
+        if (k >= prepared->batches.size() || k >= prepared->sorted.size())
+            return Status::err(EON_E_ARG, "batch index out of range");
+        const Batch& bt = prepared->batches[k];
+        if (!bt.counted) return Status::err(EON_E_ARG, "the batch's counts were never read back");
+        *window = bt.ordered ? ORDER_WINDOW : 0;
+        *bucket_lanes = bucket_lanes_route(bt, prepared->layout) ? 1 : 0;
+        if (!order || !bt.ordered) return Status::ok();
+        const SortedBufs& sb = prepared->sorted[k];
+        const size_t bytes = (size_t)bt.nb * 4;
+        if (sb.order.bytes < bytes) return Status::err(EON_E_ARG, "the batch's bucket order is not held");
+        EON_HIP(hipMemcpyAsync(order, sb.order.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
     }();

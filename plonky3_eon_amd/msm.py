@@ -178,6 +178,21 @@ class PreparedScalars:
                                                      _p(r["vals"]), _p(r["start"]), _p(r["piece_off"])))
         return r
 
+    def read_order(self, k: int, array: bool = True) -> dict:
+        """Diagnostic (eon_diag_msm_scalars_order): batch k's bucket `order` (nb entries: per `window`
+        consecutive bucket indices, those indices by run length; None for a batch that keeps none,
+        `window` 0) and whether its piece sums run one bucket per lane (`bucket_lanes`)."""
+        lib, ctx = self.ctx.lib, self.ctx
+        window, lanes = ctypes.c_uint32(), ctypes.c_uint32()
+        ctx.check(lib.eon_diag_msm_scalars_order(ctx.handle, self._h, int(k), ctypes.byref(window),
+                                                 ctypes.byref(lanes), None))
+        r = {"window": window.value, "bucket_lanes": bool(lanes.value), "order": None}
+        if array and window.value:
+            r["order"] = np.zeros(self.read_batch(k, arrays=False)["nb"], np.uint32)
+            ctx.check(lib.eon_diag_msm_scalars_order(ctx.handle, self._h, int(k), ctypes.byref(window),
+                                                     ctypes.byref(lanes), _p(r["order"])))
+        return r
+
     def close(self):
         if getattr(self, "_h", None):
             self.ctx.lib.eon_msm_scalars_destroy(self._h)
