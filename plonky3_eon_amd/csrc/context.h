@@ -123,13 +123,13 @@ struct Status {
     bool bad() const { return code != EON_OK; }
 };
 
-// device workspace of one MSM pipeline run (msm.hip); grows on demand, reused across calls
+// device workspace of one MSM pipeline run (msm.hip and its stage files); grows on demand, reused across calls
 // A batch's sorted digit pairs: keys / values by bucket, bucket starts, piece offsets.  Owned by
 // a workspace (streaming path) or by an eon_msm_scalars cache (prepared path, reused by every MSM
 // of the same scalars against other bases).
 struct SortedBufs {
     DevBuf keys2, vals2, start, piece_off;
-    DevBuf order;  // column batches: the buckets by run length per window (k_bucket_order, msm.hip)
+    DevBuf order;  // column batches: the buckets by run length per window (k_bucket_order, msm_digits.hip)
     size_t bytes() const { return keys2.bytes + vals2.bytes + start.bytes + piece_off.bytes + order.bytes; }
     void release() {
         keys2.release();
@@ -143,7 +143,7 @@ struct SortedBufs {
 struct MsmWork {
     DevBuf keys, vals, count, off2, off3, owner, piece_sums, piece_sums2, bucket_sums, red_a, red_b,
         temp, results, piece_raw, stat;
-    DevBuf canon;  // canonical scalars, column-major (the fused digit sort, msm.hip)
+    DevBuf canon;  // canonical scalars, column-major (the fused digit sort, msm_digits.hip)
     SortedBufs sorted;
     uint32_t* host_counts = nullptr;  // pinned read-back slots
     hipEvent_t counts_ev = nullptr;   // recorded after the count read-back's copies
@@ -225,7 +225,7 @@ struct eon_ctx {
     // hipMalloc/hipFree of it per proof); trimmed past MSM_SORTED_CACHE_CAP bytes
     std::vector<eon::SortedBufs> sorted_cache;
 
-    // call-wide first-level segment sums of the MSM bucket reduction (msm.hip DeferredFinish)
+    // call-wide first-level segment sums of the MSM bucket reduction (msm_batch.h DeferredFinish)
     eon::DevBuf fin_T, fin_U;
 
     // four-step DFT working blocks; the sharded MSM's partials (sharded.hip)
@@ -236,7 +236,7 @@ struct eon_ctx {
     bool van_valid = false;
     uint32_t van_log_n = 0, van_log_q = 0;
     eon::Fr van_shift{};
-    // opening bases' tables and scratch, reused across proofs (opening.hip, msm.hip)
+    // opening bases' tables and scratch, reused across proofs (opening.hip, msm_bases.hip)
     eon::DevPool pool;
 
     // scratch: NTT intermediates, host-API staging; the DIT networks' unreduced 29-limb planes

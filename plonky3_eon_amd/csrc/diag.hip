@@ -442,7 +442,7 @@ extern "C" int eon_diag_scan_chunk_counts(eon_ctx* ctx, const uint32_t* start, u
         EON_HIP(ps.take(temp, exclusive_scan_temp_bytes(m)));
         EON_HIP(ps.take(mx, 64));
         EON_HIP(hipMemcpyAsync(a.p, start, m * 4, hipMemcpyHostToDevice, ctx->stream));
-        EON_HIP(hipMemsetAsync(mx.p, 0, 16, ctx->stream));  // as batch_sort zeroes its slot (msm.hip)
+        EON_HIP(hipMemsetAsync(mx.p, 0, 16, ctx->stream));  // as batch_sort zeroes its slot (msm_digits.hip)
         EON_HIP(exclusive_scan_chunk_counts(temp.p, a.as<uint32_t>(), nb, log_chunk, b.as<uint32_t>(),
                                             mx.as<uint32_t>(), ctx->stream));
         EON_HIP(hipMemcpyAsync(out, b.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));

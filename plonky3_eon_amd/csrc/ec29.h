@@ -6,7 +6,7 @@
 //                                           ZZZ may have lazy limbs < 2^30: it only feeds mul29)
 // and every product input stays below 13p (mul29's limit, field29.h).  Affine bases are read in
 // 29-Montgomery form (x 2^261 mod p, canonical, as a 256-bit integer in the 64-byte G1Affine
-// slot; see k_table_to29 in msm.hip), so a load is a bit re-split with no product.
+// slot; see k_table_to29 in msm_bases.hip), so a load is a bit re-split with no product.
 #pragma once
 #include "ec.h"
 #include "field29.h"

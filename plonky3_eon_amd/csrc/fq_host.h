@@ -1,6 +1,6 @@
 // Host-side Fq (the BN254 G1 base field) arithmetic in 4 x 64-bit limbs, Montgomery form
 // x 2^256 mod q -- the same residues as the device's Fq (field.h), so bytes are interchangeable:
-// msm.hip converts a call's few XYZZ results to affine on the host with it (batch inversion).
+// msm_bases.hip converts a call's few XYZZ results to affine on the host with it (batch inversion).
 // Self-contained (no HIP headers): tests/fq_host_check.cpp compiles it with the host compiler.
 #pragma once
 #include <cstdint>

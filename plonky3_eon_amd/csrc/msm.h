@@ -1,4 +1,4 @@
-// Internal MSM API (see msm.hip; C ABI in include/eon.h).
+// Internal MSM API (see msm.hip; the bases object is in msm_bases.hip; C ABI in include/eon.h).
 #pragma once
 #include "context.h"
 #include "ec.h"

@@ -39,7 +39,7 @@ hipError_t radix_sort_pairs(void* temp, const uint32_t* keys_in, uint32_t* keys_
 // A sort whose FIRST pass is run by the producer of the pairs over pairs it computes instead of
 // stored ones (sort_pass.h's sort_pass_tile over its own source, one block of SORT_THREADS threads
 // and SORT_LDS bytes of LDS per tile, radix_sort_pass_args(.., 0).tiles tiles; the MSM's digit
-// pairs, msm.hip).  The histograms of every pass ready in radix_sort_histograms(temp, n):
+// pairs, msm_digits.hip).  The histograms of every pass ready in radix_sort_histograms(temp, n):
 //   radix_sort_prepare  the digit offsets of every pass and the zeroed look-back state;
 //   (the producer's first pass, with radix_sort_pass_args(temp, n, bits, 0))
 //   radix_sort_tail     passes 1 .. from the first pass's output (>= 2 passes), the last one into

@@ -8,7 +8,7 @@
 //   k_sort_pass   one launch per pass: sort_pass.h's tile (ranking in LDS, decoupled look-back,
 //                 digit-run writes) over the stored pairs.  A producer may run the first pass
 //                 itself over pairs it computes (radix_sort_prepare / radix_sort_pass_args /
-//                 radix_sort_tail; the MSM's digits, msm.hip).
+//                 radix_sort_tail; the MSM's digits, msm_digits.hip).
 // Traffic per pass: 8 B read + 8 B written per pair (plus 4 B per pair once for the histograms).
 //
 // Exclusive scan (the MSM's piece offsets, <= a few million counts): per-block sums, one block

@@ -1,6 +1,6 @@
 // One onesweep pass of the LSD radix sort (sort.hip) as a device template over the source of its
 // pairs, so that a producer can rank the pairs it computes without writing them first: sort.hip
-// instantiates it over stored (key, value) arrays, msm.hip over the MSM's digit pairs computed from
+// instantiates it over stored (key, value) arrays, msm_digits.hip over the MSM's digit pairs computed from
 // the scalars (the digit extraction fused into the first pass).
 //
 // A 1024-thread block takes the next tile of 16384 pairs (a virtual tile index from an atomic

@@ -6,7 +6,7 @@ x z^2, y z^3, z^2, z^3 times 2^261 modulo q ("29-Montgomery") plus a multiple of
 is the identity.  The documented invariant is X < 8q, Y < 4q, ZZ < 2q, ZZZ < 3q, ZZZ alone
 possibly with lazy limbs < 2^30 (the piece loop's flush negates it limb by limb).
 
-Which formula sees which inputs (msm.hip's call sites):
+Which formula sees which inputs (the call sites in msm_pieces.hip, msm_reduce.hip and msm_bases.hip):
   * madd29 / madd29_unchecked / madd29_negsum / madd29_exceptional only ever see an accumulator
     built in registers from a base (canonical X, Y, ZZ = ZZZ = one), their own output or
     dbl29_affine's: ZZZ normalised below 2q.  The base is canonical; madd29_negsum alone also

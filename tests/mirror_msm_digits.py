@@ -1,4 +1,4 @@
-"""Plain-Python restatement of the MSM's digit pipeline (msm.hip: k_msm_digits, k_msm_digits4,
+"""Plain-Python restatement of the MSM's digit pipeline (msm_digits.hip: k_msm_digits, k_msm_digits4,
 DigitSource; k_bucket_start; the piece offsets of sort.h), for the stage-level tests.
 
 Signed-window recoding of a canonical scalar s into W windows of c bits, B = 2^(c-1): window w's raw
@@ -83,7 +83,7 @@ def reference_pairs(cols, c: int, W: int, ref_windows: int, fixed: bool):
 
 
 def bucket_of(keys: np.ndarray, c: int, groups: int, nb: int) -> np.ndarray:
-    """msm.hip bucket_of: (|d| - 1) groups + group, nb for the sentinel."""
+    """msm_batch.h bucket_of: (|d| - 1) groups + group, nb for the sentinel."""
     k = keys.astype(np.uint64)
     b = (k & np.uint64((1 << (c - 1)) - 1)) * np.uint64(groups) + (k >> np.uint64(c))
     return np.where(keys == np.uint32(SENTINEL), np.uint64(nb), b).astype(np.int64)

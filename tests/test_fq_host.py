@@ -1,4 +1,4 @@
-"""CPU: the host-side Fq inverse msm.hip converts MSM results with (plonky3_eon_amd/csrc/fq_host.h;
+"""CPU: the host-side Fq inverse msm_bases.hip converts MSM results with (plonky3_eon_amd/csrc/fq_host.h;
 binary extended Euclid): inverse(x 2^256) = x^-1 2^256 mod q for canonical and
 non-canonical inputs, and 0 for a = 0 mod q (0, q, 2q -- the loop must end instead of spinning on
 u = 0), against Python's pow; plus the CIOS product it relies on."""

@@ -268,7 +268,7 @@ def test_columns_fused_reduce_edge_cases(gpu_ctx):
 @pytest.mark.parametrize("cancel", [False, True])
 def test_columns_piece_merge(gpu_ctx, rows, cancel):
     """Buckets straddling piece-sum chunk boundaries (k_piece_sum29's in-wave merge and
-    k_piece_merge29 between waves, msm.hip): 64 columns of `rows` equal scalars over bases all P
+    k_piece_merge29 between waves, msm_pieces.hip): 64 columns of `rows` equal scalars over bases all P
     (or P then -P), so every bucket is a run of `rows` sorted pairs laid end to end and the
     16-pair chunks cut them -- 24 rows: two unequal pieces, a run across the chunk-64 wave
     boundary; 32: two equal pieces (the merge doubles); 48: three pieces (no merge); with -P
@@ -327,7 +327,7 @@ REDUCE_ROUTES = {
 
 @pytest.mark.parametrize("route", list(REDUCE_ROUTES))
 def test_reduce_routes(gpu_ctx, monkeypatch, route):
-    """The six routes of the bucket reduction (reduce_route, msm.hip), each at the smallest shape
+    """The six routes of the bucket reduction (reduce_route, msm_reduce.hip), each at the smallest shape
     that reaches it and named by the profiler records it leaves:
     Deferred         fixed-base, 66 columns x 256 rows (c = 8, B = 128): >= 64 groups, one finish
                      launch per call;

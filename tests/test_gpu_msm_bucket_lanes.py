@@ -1,6 +1,6 @@
-"""The one-bucket-per-lane piece sums of column batches (k_bucket_order + k_piece_sum_bucket29,
-msm.hip): the bucket order a prepared batch keeps, read back through eon_diag_msm_scalars_order
-and checked exactly, the route every batch reports, and every column against the C Pippenger
+"""The one-bucket-per-lane piece sums of column batches (k_bucket_order in msm_digits.hip,
+k_piece_sum_bucket29 in msm_pieces.hip): the bucket order a prepared batch keeps, read back through
+eon_diag_msm_scalars_order and checked exactly, the route every batch reports, and every column against the C Pippenger
 restatement (or the Python double-and-add oracle where the bases repeat)."""
 
 import numpy as np
@@ -15,7 +15,7 @@ from test_gpu_msm_digits import column, to_matrix
 pytestmark = pytest.mark.gpu
 
 ORDER_CAP = 1023  # k_bucket_order sorts run lengths up to here; longer ones compare equal (eon.h)
-PIECE = 32  # the chunked route's one-level bound: pieces of one bucket (msm.hip)
+PIECE = 32  # the chunked route's one-level bound: pieces of one bucket (msm_batch.h)
 
 
 def fr(x):
@@ -39,8 +39,8 @@ def dev(mat):
 def check_order(prep):
     """Every batch's order against its own bucket starts: per window a permutation of the window's
     bucket indices, run lengths non-decreasing along it, equal lengths in index order.
-    The reported route is the rule's (msm.hip bucket_lanes_route): >= 64 groups, no bucket above
-    PIECE pieces of the chunked route, no run above ORDER_CAP.
+    The reported route is the rule's (msm_digits.hip bucket_lanes_route): >= 64 groups, no bucket
+    above PIECE pieces of the chunked route, no run above ORDER_CAP.
     -> per batch (bucket_lanes, the run lengths)."""
     out = []
     for k in range(prep.num_batches()):
@@ -188,7 +188,8 @@ def test_skewed_batch_takes_chunks(gpu_ctx, monkeypatch):
 def test_prepared_reuses_order(gpu_ctx, monkeypatch):
     """prepare_columns once, then the prepared MSMs against two other bases of the same layout: each
     equals a fresh msm_columns against that base, on the bucket route, and the order read back after
-    both passes is the commitment's."""
+    both passes is the commitment's.  Then the same for a batch whose stored plan is the chunked
+    piece sums and the CombineGroups route."""
     monkeypatch.setenv("EON_MSM_FORCE_C", "8")
     rows, width = 512, 66
     mat = C.random_fr(66, rows * width).reshape(rows, width, 4)
@@ -209,6 +210,37 @@ def test_prepared_reuses_order(gpu_ctx, monkeypatch):
             after = prep.read_order(0)
             assert after["bucket_lanes"]
             np.testing.assert_array_equal(after["order"], before)
+    finally:
+        prep.close()
+        for b in bases:
+            b.close()
+    # A stored plan other than the default one: test_gpu_msm._route_combine_groups' input, 66 columns
+    # x 256 rows (c = 8) with column 0 the scalar 0x0101...01 in every row -- 512 pieces in one bucket,
+    # so chunked piece sums and the CombineGroups route -- multiplied against two bases objects in
+    # one call.
+    monkeypatch.delenv("EON_MSM_FORCE_C")
+    rows = 256
+    mat = C.random_fr(56, rows * width).reshape(rows, width, 4)
+    mat[:, 0] = fr(int.from_bytes(b"\x01" * 32, "little"))
+    pts = [srs_powers(rows, 2000 + t, gpu_ctx) for t in range(3)]
+    bases = [MsmBases(p, gpu_ctx, precompute=True) for p in pts]
+    got, prep = bases[0].prepare_columns(dev(mat))
+    try:
+        (lanes, _), = check_order(prep)
+        assert not lanes
+        gpu_ctx.profile(True)
+        try:
+            res = prep.msm([bases[1], bases[2]])
+            kernels = set(gpu_ctx.profile_report())
+        finally:
+            gpu_ctx.profile(False)
+        assert {"k_partial_combine", "bucket_reduce"} <= kernels and "k_group_finish" not in kernels, sorted(kernels)
+        for t in (1, 2):
+            np.testing.assert_array_equal(res[t - 1], bases[t].msm_columns(mat))
+            for j in range(width):
+                np.testing.assert_array_equal(res[t - 1][j], C.g1_msm(pts[t], mat[:, j]),
+                                              err_msg=f"bases {t} column {j}")
+        assert not prep.read_order(0)["bucket_lanes"]
     finally:
         prep.close()
         for b in bases:

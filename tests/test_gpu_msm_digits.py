@@ -1,4 +1,4 @@
-"""The MSM digit pipeline stage by stage (msm.hip: k_msm_digits, k_msm_digits4, the fused
+"""The MSM digit pipeline stage by stage (msm_digits.hip: k_msm_digits, k_msm_digits4, the fused
 k_digit_sort_pass over DigitSource, the radix sort, k_bucket_start, the piece offsets) against the
 Python recoding of mirror_msm_digits: what a prepared handle keeps of every batch is read back and
 compared exactly, on every digit route and at window widths forced through EON_MSM_FORCE_C to reach
@@ -22,7 +22,7 @@ R = O.P
 
 
 def choose_c(n, fixed):
-    """msm.hip choose_c: the width minimising n W mixed additions + 6 additions per bucket."""
+    """msm_bases.hip choose_c: the width minimising n W mixed additions + 6 additions per bucket."""
     best, best_cost = 4, float("inf")
     for c in range(4, 21):
         W = (255 + c - 1) // c
@@ -227,7 +227,7 @@ def single_column(bits, rows, c, seed):
 @pytest.mark.parametrize("bits", [45, 48])
 def test_single_msm_window_truncation(gpu_ctx, monkeypatch, bits, fixed):
     """The single MSM digitises only the windows its largest scalar reaches, one more for the carry
-    (k_scalar_or, msm_run_columns); fixed-base references stay row x the layout's windows + window.
+    (k_scalar_or, active_windows); fixed-base references stay row x the layout's windows + window.
     Its batch, kept by the diagnostic entry that runs that same route, is compared with the
     reference recoded at the kept window count: the count comes from the info, is the expected
     ceil((bits + 1) / c) -- well below the layout's -- and every window it drops holds only zero

@@ -1,7 +1,7 @@
 """Instruction mix of a kernel's basic blocks in a gfx950 assembly listing.
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude --cuda-device-only -S \
-        plonky3_eon_amd/csrc/msm.hip -o /tmp/msm.s
+        plonky3_eon_amd/csrc/msm_pieces.hip -o /tmp/msm_pieces.s
     python tools/isa_count.py /tmp/msm.s k_piece_sum29 [--blocks N] [--costs profiles/r06/s4/ubench_isa2.txt]
 
 Prints the N largest basic blocks of the first function whose symbol contains the substring,
