@@ -257,6 +257,8 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   16: many checks in one pass -- eon_multi_pairing_many, eon_kzg_verify_batch_many and
+ *       eon_air_eval_at_points_dev, additive;
  *   15: eon_diag_msm_scalars_order, a column batch's bucket order and piece-sum route, additive;
  *   14: eon_g1_compress[_dev], the inverse of eon_g1_decompress[_dev], and EON_E_FORMAT, additive;
  *   13: eon_fr_fold_columns_dev, the gamma-fold of the batched KZG opening, additive;
@@ -706,6 +708,22 @@ int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog, uint32_
                               const eon_fr* publics, uint32_t n_public, const eon_fr* challenges,
                               uint32_t n_challenges, eon_fr* out);
 
+/* The same evaluation for n proofs of one program in ONE launch (kernel k_air_points: block i is
+ * proof i, one lane live as above, so the n dependent chains run side by side).  `rows` is a DEVICE
+ * array of n x row_stride canonical Fr; row i holds proof i's opened values as
+ * local | next | pre_local | pre_next | perm_local | perm_next (width, width, preprocessed_width x 2,
+ * permutation_width x 2; row_stride at least their sum, EON_E_SHAPE otherwise).  Host arrays:
+ * log_n[n], zeta[n], alpha[n], publics (n x the program's public value count), challenges
+ * (n x n_challenges), out (2 n: out[2 i] the folded value of proof i, out[2 i + 1] the quotient
+ * side).  Every pair is bit-identical to eon_air_eval_at_point_dev on the same inputs.  The errors
+ * are that call's; one caused by proof i's inputs (a zeta_i on its trace domain, a value that is not
+ * canonical, log_n[i] > 28) has a message that starts "point i: ".  n = 0 writes nothing.  The
+ * register file follows the same rule: each block its own LDS, or row i of n rows of the global
+ * buffer. */
+int eon_air_eval_at_points_dev(eon_ctx* ctx, const eon_air_program* prog, uint32_t n, const uint32_t* log_n,
+                               const eon_fr* zeta, const eon_fr* alpha, const eon_fr* rows, uint64_t row_stride,
+                               const eon_fr* publics, const eon_fr* challenges, uint32_t n_challenges, eon_fr* out);
+
 /* out[i] = sum_{j<k} coeffs[j] * in[j * rows + i] (device in/out, host coeffs, 1 <= k <= 64):
  * the combine step of the lane-sharded quotient -- every rank all-gathers the
  * shards' partial quotients and weights shard g by alpha^(K_lane * (VECTOR_LEN - lane_end_g)). */
@@ -852,6 +870,28 @@ int eon_multi_pairing(eon_ctx* ctx, const eon_g1_affine* p, const eon_g2_affine*
 int eon_kzg_verify_batch(eon_ctx* ctx, const eon_g1_affine* commitments, const eon_g1_affine* witnesses,
                          const eon_fr* values, const eon_fr* points, uint64_t n, const eon_g2_affine* g2_alpha,
                          int* ok);
+
+/* Many independent checks in one pass.  `seg` (host) holds nseg + 1 ascending offsets with
+ * seg[0] = 0: segment s is items [seg[s], seg[s + 1]) of the arrays, seg[nseg] their length.  One
+ * Miller launch covers every pair; the final exponentiation runs one block per segment, so every
+ * segment keeps its own Gt product (no random weights across segments).  nseg = 0 writes nothing;
+ * seg not ascending from 0 is EON_E_ARG; more than 2^24 segments is EON_E_SHAPE.
+ *
+ * eon_multi_pairing_many: out[s] = prod_{i in segment s} e(p[i], q[i]), each limb for limb what
+ *   eon_multi_pairing gives for that slice (the identity of Gt for an empty segment).  Arguments
+ *   are validated as in eon_multi_pairing (any bad point fails the call).
+ * eon_kzg_verify_batch_many: segment s holds the openings of one verify_batch.  status[s] = 1 when
+ *   its product is the identity (an empty segment is 1), 0 when it is not, and EON_E_ARG when the
+ *   segment holds a commitment or witness that is not a G1 point or a value or point that is not a
+ *   canonical Fr -- per segment: such a segment is left out of the device work, the others are
+ *   still checked and the call returns EON_OK (eon_kzg_verify_batch on that segment alone gives
+ *   the message).  The openings are grouped by distinct point per segment; k_vb_sums / k_vb_pairs
+ *   run sum_s (G_s + 1) blocks in one launch each.  A null or invalid g2_alpha fails the call. */
+int eon_multi_pairing_many(eon_ctx* ctx, const eon_g1_affine* p, const eon_g2_affine* q, const uint64_t* seg,
+                           uint32_t nseg, eon_fq12* out);
+int eon_kzg_verify_batch_many(eon_ctx* ctx, const eon_g1_affine* commitments, const eon_g1_affine* witnesses,
+                              const eon_fr* values, const eon_fr* points, const uint64_t* seg, uint32_t nseg,
+                              const eon_g2_affine* g2_alpha, int* status);
 
 /* ---- KzgMmcs: Mmcs<Fr> over the same SRS (kzg/src/mmcs.rs) -----------------------------------
  * A batch of matrices of mixed heights (any height >= 1, powers of two or not), every column a

@@ -478,7 +478,45 @@ int eon_proof_peek(const uint8_t* bytes, uint64_t len, eon_proof_shape* shape, e
 int eon_proof_deserialize(eon_ctx* ctx, const uint8_t* bytes, uint64_t len, eon_proof_lk* out,
                           eon_proof_io_report* report);
 
-/* bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
+/* ---- verifying many proofs in one pass ----------------------------------------------------------
+ * n proofs of ONE program against one pcs, one verdict per proof: results[i] -- and the detail, the
+ * challenges reported and the end state of challenger i -- is exactly what eon_verify_air[_fs] gives
+ * for proof i alone.  The three phases of the verifier run over the whole batch: the host part of
+ * every proof (shapes, transcript, the opening list, quotient(zeta)) on min(n, 8) threads; the
+ * openings of every proof still standing in ONE eon_kzg_verify_batch_many, a segment per proof (each
+ * proof keeps its own Gt product: no random weights across proofs, and a bad proof is located
+ * without bisection); ONE eon_air_eval_at_points_dev over the proofs whose openings passed.
+ *   proofs: n eon_proof_lk.  publics: n x n_public.  The verifier key is shared (one AIR).
+ *   eon_verify_air_many: challenges n x n_challenges, alphas[n], zetas[n]; in the batched opening
+ *     mode gammas[n] / deltas[n], or NULL for the pcs's eon_kzg_pcs_set_opening_challenges pair.
+ *     (The arrays are there because result i must be eon_verify_air's for proof i: a proof made
+ *     with given challenges carries its OWN gamma and delta, and the pcs holds one pair.  For the
+ *     same reason eon_verify_many_opening_challenges reports, per proof, what
+ *     eon_kzg_pcs_last_opening_challenges reports for a single verify.)
+ *   eon_verify_air_many_fs: n distinct challengers, advanced as eon_verify_air_fs advances one;
+ *     challenges_out (n x the program's challenge count), alphas_out[n], zetas_out[n] may be NULL
+ *     and entry i is left unwritten for a shape-rejected proof.
+ * Every proof of a call uses the pcs's current opening mode.  What is an error code (not a verdict)
+ * in eon_verify_air is one here, its message starting "proof i: ", and no verdicts are written.
+ * After EON_OK, eon_kzg_pcs_last_error holds the first rejected proof's reason as "proof i: ..."
+ * (empty when all are valid), eon_verify_many_detail(pcs, i) the reason of proof i (empty when
+ * valid; NULL for an index past the last call's n; valid until the next call on the pcs), and
+ * eon_verify_many_opening_challenges the gamma / delta used for proof i in the batched mode.
+ * n = 0 writes nothing. */
+int eon_verify_air_many(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proofs, uint32_t n,
+                        const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                        const eon_g1_affine* vk_commitment, const eon_fr* challenges, uint32_t n_challenges,
+                        const eon_fr* alphas, const eon_fr* zetas, const eon_fr* gammas, const eon_fr* deltas,
+                        int* results);
+int eon_verify_air_many_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proofs, uint32_t n,
+                           const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                           const eon_g1_affine* vk_commitment, eon_challenger* const* challengers, int* results,
+                           eon_fr* challenges_out, eon_fr* alphas_out, eon_fr* zetas_out);
+const char* eon_verify_many_detail(const eon_kzg_pcs* pcs, uint32_t i);
+int eon_verify_many_opening_challenges(const eon_kzg_pcs* pcs, uint32_t i, eon_fr* gamma, eon_fr* delta);
+
+/* 11: eon_verify_air_many[_fs], eon_verify_many_detail / _opening_challenges, additive.
+ * bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
  * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; 8:
  * eon_kzg_pcs_create_from_srs[_bytes] and eon_kzg_pcs_create_verifier; 9: the opening mode,
  * eon_kzg_pcs_set_opening and its challenges; 10: the proof bytes, eon_proof_bytes_size / _serialize /

@@ -34,7 +34,7 @@ EON_ORDER_BITREV = 1
 EON_FOURSTEP_NATURAL = 0
 EON_FOURSTEP_TRANSPOSED = 1
 EON_MSM_PRECOMPUTE = 1
-ABI_VERSION = 15  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
+ABI_VERSION = 16  # include/eon.h eon_abi_version(): the layouts below (eon_collective, eon_g2_affine, ...)
 
 _ERRNAMES = {
     EON_E_SHAPE: "EON_E_SHAPE",
@@ -181,6 +181,8 @@ SIGNATURES = {
     "eon_g2_mul": (_INT, [_P, _P, _P, _P]),
     "eon_multi_pairing": (_INT, [_P, _P, _P, _U64, _P]),
     "eon_kzg_verify_batch": (_INT, [_P, _P, _P, _P, _P, _U64, _P, ctypes.POINTER(ctypes.c_int)]),
+    "eon_multi_pairing_many": (_INT, [_P, _P, _P, _P, _U32, _P]),
+    "eon_kzg_verify_batch_many": (_INT, [_P, _P, _P, _P, _P, _P, _U32, _P, _P]),
     "eon_g1_srs_powers_dev": (_INT, [_P, _P, _U64, _P]),
     "eon_g1_decompress_dev": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
     "eon_g1_decompress": (_INT, [_P, _P, _U64, _P, ctypes.POINTER(eon_srs_report)]),
@@ -219,6 +221,7 @@ SIGNATURES = {
     "eon_lookup_permutation_dev": (_INT, [_P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P]),
     "eon_check_constraints_dev": (_INT, [_P, _P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P, _P]),
     "eon_air_eval_at_point_dev": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _U32, _P]),
+    "eon_air_eval_at_points_dev": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _U64, _P, _P, _U32, _P]),
     "eon_fr_lincomb_dev": (_INT, [_P, _P, _U32, _U64, _P, _P]),
     "eon_fr_fold_columns_dev": (_INT, [_P, _P, _U64, _U32, _P, _P, _P]),
     "eon_fourstep_twiddle_pack_dev": (_INT, [_P, _P, _U32, _U32, _U64, _U32, _U32, _P]),

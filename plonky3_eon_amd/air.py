@@ -330,6 +330,51 @@ class AirProgram:
             ch.ctypes.data_as(ctypes.c_void_p), len(challenges), out.ctypes.data_as(ctypes.c_void_p)))
         return tuple(fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v))) for v in out)
 
+    def eval_at_points(self, log_ns, zetas, alphas, rows, publics=None, challenges=None):
+        """eval_at_point for n proofs in one launch (eon_air_eval_at_points_dev).  `rows`: an
+        (n, row_stride, 4) device tensor, row i = proof i's opened values local | next |
+        preprocessed_local | preprocessed_next | permutation_local | permutation_next; `log_ns`,
+        `zetas`, `alphas`: n canonical ints each; `publics` / `challenges`: per proof a sequence of the
+        program's public values / challenges (None when the program has none).  Returns a list of n
+        pairs, each what eval_at_point returns for that proof."""
+        import torch
+
+        from .field import fr_unmont
+
+        n = len(zetas)
+        if len(log_ns) != n or len(alphas) != n:
+            raise ValueError("one log_n and one alpha per zeta")
+        publics = [()] * n if publics is None else list(publics)
+        challenges = [()] * n if challenges is None else list(challenges)
+        if len(publics) != n or len(challenges) != n:
+            raise ValueError("one sequence of public values and of challenges per proof")
+        n_ch = len(challenges[0]) if n else 0
+        if any(len(p) != self.n_public for p in publics) or any(len(c) != n_ch for c in challenges):
+            raise ValueError("every proof needs the program's public values and the same number of challenges")
+        if n == 0:
+            return []
+        rows = rows.contiguous()
+        if rows.dim() != 3 or rows.shape[0] != n or rows.shape[2] != 4:
+            raise ValueError(f"rows must be ({n}, row_stride, 4)")
+        lg = np.asarray(log_ns, dtype=np.uint32)
+        z = _publics_limbs(zetas)
+        a = _publics_limbs(alphas)
+        def flat(seqs):  # per proof canonical ints, or (k, 4) Montgomery limbs
+            if seqs and isinstance(seqs[0], np.ndarray) and seqs[0].ndim == 2:
+                return np.concatenate(seqs)
+            return [v for s in seqs for v in s]
+
+        pub = _publics_limbs(flat(publics))
+        ch = _publics_limbs(flat(challenges))
+        out = np.zeros((2 * n, 4), np.uint64)
+        self.ctx.set_stream(torch.cuda.current_stream(rows.device).cuda_stream)
+        self.ctx.check(self.ctx.lib.eon_air_eval_at_points_dev(
+            self.ctx.handle, self._h, n, *[x.ctypes.data_as(ctypes.c_void_p) for x in (lg, z, a)], _dp(rows),
+            int(rows.shape[1]), pub.ctypes.data_as(ctypes.c_void_p), ch.ctypes.data_as(ctypes.c_void_p), n_ch,
+            out.ctypes.data_as(ctypes.c_void_p)))
+        vals = [fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v))) for v in out]
+        return [(vals[2 * i], vals[2 * i + 1]) for i in range(n)]
+
     def quotient_values(self, lde, log_n: int, log_qd: int, alpha, publics=(), preprocessed_lde=None,
                         permutation_lde=None, challenges=()):
         """quotient_values (prover.rs:539-709) on the trace's LDE over GENERATOR * K (natural);

@@ -598,6 +598,37 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_point(const CodeBlock* __rest
     st_vec(out + 1, pack29<FrP>(canon29<FrP>(quot)));
 }
 
+// k_air_point at many points: block i is the evaluation of proof i, one wave's lane 0 live exactly
+// as above, so a batch costs one launch and the proofs run side by side.  Proof i's opened values
+// are row i of `rows` (row_stride Fr): local | next | pre_local | pre_next | perm_local | perm_next;
+// its four selectors are sels[4 i ..], its alpha alphas[i], its constant table (the program's
+// constants, then its own publics and challenges) tables[i * table_stride ..], its results
+// out[2 i], out[2 i + 1].  Registers: the block's own LDS, or row i of the n rows of `gregs`.
+template <int MODE, bool PRE, bool PERM>
+__global__ void __launch_bounds__(AIR_BLOCK) k_air_points(const CodeBlock* __restrict__ code, uint32_t n_blocks,
+                                                      uint32_t n_regs, const Fr* __restrict__ rows,
+                                                      uint64_t row_stride, uint32_t width, uint32_t pre_width,
+                                                      uint32_t perm_width, const F29* __restrict__ tables,
+                                                      uint32_t table_stride, const Fr* __restrict__ sels,
+                                                      const Fr* __restrict__ alphas, Fr* __restrict__ out,
+                                                      uint4* __restrict__ gregs) {
+    extern __shared__ uint4 lds_regs[];
+    if (threadIdx.x != 0) return;
+    const uint32_t i = blockIdx.x;
+    const Fr* const local = rows + (uint64_t)i * row_stride;
+    const Fr* const pre = local + 2 * width;
+    const Fr* const perm = pre + 2 * pre_width;
+    const auto w = make_window<PRE, PERM>(local, local + width, pre, pre + pre_width, perm, perm + perm_width, width,
+                                          pre_width, 0, 0, 0, 1, tables + (uint64_t)i * table_stride, sels + 4 * i);
+    MemRegs rf = reg_file<MODE>(n_regs, lds_regs, gregs, MODE == 0 ? 0 : i, MODE == 0 ? blockDim.x : gridDim.x);
+    F29 acc = zero29();
+    run_program(code, n_blocks, rf, w, uniform29(shl5_to261<FrP>(ld_pinned(alphas + i))), acc);
+    const F29 folded = mul29<FrP>(acc, const29<FrP>(R29<FrP>::TO256));
+    const F29 quot = mul29<FrP>(acc, unpack29(ld_pinned(w.sels + 3)));
+    st_vec(out + 2 * i, pack29<FrP>(canon29<FrP>(folded)));
+    st_vec(out + 2 * i + 1, pack29<FrP>(canon29<FrP>(quot)));
+}
+
 }  // namespace
 
 struct eon_air_program {
@@ -617,6 +648,8 @@ struct eon_air_program {
     DevBuf d_code, d_table, d_sels, d_regs;
     DevBuf d_check;  // eon_check_constraints_dev: min key | failures | value | per-constraint counts
     DevBuf d_point;  // eon_air_eval_at_point_dev: the four selectors at zeta | the two results
+    // eon_air_eval_at_points_dev, for n proofs: 4n selectors | 2n results | n alphas | n constant tables
+    DevBuf d_points;
     std::vector<Fr> staged;  // host copy of the table for the current launch
     std::vector<F29> staged29;  // the same in the device's form (x 2^261, < 2p)
 };
@@ -772,9 +805,29 @@ Status stage_table(eon_ctx* ctx, eon_air_program* prog, const eon_fr* publics, u
     return Status::ok();
 }
 
+// selectors_at_point of the trace domain of 2^log_n rows (shift 1), commit/src/domain.rs:237-246,
+// exact on the host: Z_H = zeta^N - 1, out = is_first_row = Z_H / (zeta - 1) | is_last_row =
+// Z_H / (zeta - h^-1) | is_transition = zeta - h^-1 | inv_vanishing = 1 / Z_H.  The reference panics
+// (inverse of zero) where one of the three divisors vanishes.
+Status selectors_at_point(uint32_t log_n, const Fr& z, Fr out[4]) {
+    Fr zn = z;
+    for (uint32_t i = 0; i < log_n; i++) zn = sqr(zn);
+    const Fr z_h = sub(zn, Fr::one());
+    const Fr h_inv = inverse(fr_two_adic_generator(log_n));
+    const Fr d_first = sub(z, Fr::one()), d_last = sub(z, h_inv);
+    if (z_h.is_zero() || d_first.is_zero() || d_last.is_zero())
+        return Status::err(EON_E_ARG, "zeta lies on the trace domain: the selectors at zeta are undefined "
+                                      "(the reference's inverse of zero)");
+    out[0] = mul(z_h, inverse(d_first));
+    out[1] = mul(z_h, inverse(d_last));
+    out[2] = d_last;
+    out[3] = inverse(z_h);
+    return Status::ok();
+}
+
 void release_program(eon_air_program* p) {
     for (DevBuf* b : {&p->d_code, &p->d_table, &p->d_sels, &p->d_regs, &p->d_desc, &p->d_terms, &p->d_flag,
-                      &p->d_check, &p->d_point})
+                      &p->d_check, &p->d_point, &p->d_points})
         b->release();
     if (p->terms) release_program(p->terms.get());
 }
@@ -1463,19 +1516,8 @@ int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint3
         const Fr al = fr_from_abi(alpha), z = fr_from_abi(zeta);
         if (!fr_is_canonical(al)) return Status::err(EON_E_ARG, "alpha is not a canonical Fr");
         if (!fr_is_canonical(z)) return Status::err(EON_E_ARG, "zeta is not a canonical Fr");
-        // selectors_at_point of the trace domain (shift 1), commit/src/domain.rs:237-246, exact on the
-        // host: Z_H = zeta^N - 1, is_first_row = Z_H / (zeta - 1), is_last_row = Z_H / (zeta - h^-1),
-        // is_transition = zeta - h^-1, inv_vanishing = 1 / Z_H.  The reference panics (inverse of
-        // zero) where one of the three divisors vanishes.
-        Fr zn = z;
-        for (uint32_t i = 0; i < log_n; i++) zn = sqr(zn);
-        const Fr z_h = sub(zn, Fr::one());
-        const Fr h_inv = inverse(fr_two_adic_generator(log_n));
-        const Fr d_first = sub(z, Fr::one()), d_last = sub(z, h_inv);
-        if (z_h.is_zero() || d_first.is_zero() || d_last.is_zero())
-            return Status::err(EON_E_ARG, "zeta lies on the trace domain: the selectors at zeta are undefined "
-                                          "(the reference's inverse of zero)");
-        const Fr sel_host[4] = {mul(z_h, inverse(d_first)), mul(z_h, inverse(d_last)), d_last, inverse(z_h)};
+        Fr sel_host[4];
+        EON_TRY(selectors_at_point(log_n, z, sel_host));
         EON_TRY(stage_table(ctx, prog, publics, n_public, challenges, n_challenges));
         EON_HIP(prog->d_point.ensure(6 * sizeof(Fr)));
         Fr* sels = prog->d_point.as<Fr>();
@@ -1496,6 +1538,79 @@ int eon_air_eval_at_point_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint3
             prog->pre_width, prog->d_table.as<F29>(), sels, al, res));
         static_assert(sizeof(Fr) == sizeof(eon_fr), "Fr is the ABI's 32 little-endian bytes");
         EON_HIP(hipMemcpyAsync(out, res, 2 * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
+        EON_HIP(hipStreamSynchronize(ctx->stream));
+        return Status::ok();
+    });
+}
+
+int eon_air_eval_at_points_dev(eon_ctx* ctx, const eon_air_program* prog_c, uint32_t n, const uint32_t* log_n,
+                               const eon_fr* zeta, const eon_fr* alpha, const eon_fr* rows, uint64_t row_stride,
+                               const eon_fr* publics, const eon_fr* challenges, uint32_t n_challenges, eon_fr* out) {
+    if (!ctx || !prog_c) return EON_E_ARG;
+    auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
+    return with_ctx(ctx, [&]() -> Status {
+        if (n == 0) return Status::ok();
+        const uint64_t opened = 2 * ((uint64_t)prog->width + prog->pre_width + prog->perm_width);
+        EON_TRY(check_args(ctx, prog, !log_n || !zeta || !alpha || !out || (opened && !rows), MatArg::none(),
+                           MatArg::none(), publics, prog->n_public, challenges, n_challenges));
+        if (row_stride < opened) return Status::err(EON_E_SHAPE, "row_stride is below the program's opened values");
+        if (n > (1u << 20)) return Status::err(EON_E_SHAPE, "at most 2^20 points");
+        const auto at = [](uint32_t i, const std::string& what) { return "point " + std::to_string(i) + ": " + what; };
+        // per proof: the selectors at its zeta, its alpha, and its copy of the constant table
+        // (stage_table's layout: program constants ++ public values ++ challenges)
+        const uint32_t n_public = prog->n_public;
+        const uint32_t table_stride = (uint32_t)prog->consts.size() + n_public + n_challenges;
+        std::vector<Fr> head(7 * (size_t)n);  // 4n selectors | 2n results (unset) | n alphas
+        std::vector<F29> tables((size_t)n * table_stride);
+        for (uint32_t i = 0; i < n; i++) {
+            if (log_n[i] > 28) return Status::err(EON_E_SHAPE, at(i, "log_n must be <= 28 (Fr::TWO_ADICITY)"));
+            const Fr al = fr_from_abi(&alpha[i]), z = fr_from_abi(&zeta[i]);
+            if (!fr_is_canonical(al)) return Status::err(EON_E_ARG, at(i, "alpha is not a canonical Fr"));
+            if (!fr_is_canonical(z)) return Status::err(EON_E_ARG, at(i, "zeta is not a canonical Fr"));
+            const Status sel = selectors_at_point(log_n[i], z, &head[4 * (size_t)i]);
+            if (sel.bad()) return Status::err(sel.code, at(i, sel.msg));
+            head[6 * (size_t)n + i] = al;
+            F29* t = tables.data() + (size_t)i * table_stride;
+            for (const Fr& c : prog->consts) *t++ = shl5_to261<FrP>(c);
+            for (uint32_t j = 0; j < n_public + n_challenges; j++) {
+                const bool pub = j < n_public;
+                const Fr v = fr_from_abi(pub ? &publics[(size_t)i * n_public + j]
+                                             : &challenges[(size_t)i * n_challenges + (j - n_public)]);
+                if (!fr_is_canonical(v))
+                    return Status::err(EON_E_ARG, at(i, pub ? "public value is not a canonical Fr"
+                                                            : "challenge is not a canonical Fr"));
+                *t++ = shl5_to261<FrP>(v);
+            }
+        }
+        const size_t head_bytes = head.size() * sizeof(Fr), table_bytes = tables.size() * sizeof(F29);
+        EON_HIP(prog->d_points.ensure(head_bytes + std::max<size_t>(table_bytes, sizeof(F29))));
+        Fr* sels = prog->d_points.as<Fr>();
+        Fr* res = sels + 4 * (size_t)n;
+        const Fr* alphas = sels + 6 * (size_t)n;
+        F29* d_tables = reinterpret_cast<F29*>(prog->d_points.as<char>() + head_bytes);
+        RegFile regs;  // one register row per proof
+        EON_TRY(plan_regs(prog, n, &regs));
+        // from here on the stream reads `head` and `tables`: every path out synchronises first
+        const auto drained = [&](Status s) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return s;
+        };
+        EON_HIP(hipMemcpyAsync(sels, head.data(), head_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (table_bytes) {
+            const hipError_t e = hipMemcpyAsync(d_tables, tables.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return drained(Status::err(EON_E_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e)));
+        }
+        const Profile prof{"k_air_points", (uint64_t)n * (opened * 32 + 7 * 32),
+                           (uint64_t)n * (products(prog->code, true) + 2)};
+        // one block of regs.block threads per proof: launch_air sizes the grid from the rows
+        const Status launched = launch_air(
+            ctx, prog, regs, (uint64_t)n * regs.block, code_blocks(prog->code.size()), prof, prog->pre_width > 0,
+            prog->perm_width > 0, [](auto m, auto pre, auto perm) { return k_air_points<m(), pre(), perm()>; },
+            reinterpret_cast<const Fr*>(rows), row_stride, prog->width, prog->pre_width, prog->perm_width,
+            const_cast<const F29*>(d_tables), table_stride, const_cast<const Fr*>(sels), alphas, res);
+        if (launched.bad()) return drained(launched);
+        const hipError_t e = hipMemcpyAsync(out, res, 2 * (size_t)n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) return drained(Status::err(EON_E_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e)));
         EON_HIP(hipStreamSynchronize(ctx->stream));
         return Status::ok();
     });

@@ -339,7 +339,7 @@ hipError_t ctx_ensure(eon_ctx* ctx, DevBuf& b, size_t need) {
 
 extern "C" {
 
-uint32_t eon_abi_version(void) { return 15; }
+uint32_t eon_abi_version(void) { return 16; }
 
 int eon_ctx_create(int device_ordinal, eon_ctx** out) {
     if (!out) return EON_E_ARG;

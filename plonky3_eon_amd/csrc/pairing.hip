@@ -15,13 +15,18 @@
 //   k_vb_pairs    the merged pairs: P_0 = sum C - (sum v) G1 with Q_0 = G2, P_z = -sum W with
 //                 Q_z = [alpha]G2 - z G2 (fixed-generator multiples as sums of 2^i tables, 64
 //                 lanes and an LDS tree per pair, then affine)
+//                 Both run over the blocks of SEVERAL independent verify_batch checks at once
+//                 (eon_kzg_verify_batch_many): a descriptor per block (VbBlock) says which openings
+//                 it sums and whether it is a point's block or the commitments'; block b's pair is
+//                 pair b
 //   k_miller_team one 6-lane team per pair (pairing_team.h: lane k holds the coefficient of w^k):
 //                 f_{6x+2,Q}(P) by the signed digits of 6x + 2 and the two Frobenius-twisted lines,
 //                 T in projective coordinates (no inversions; lines scaled by Fq2 factors), the
 //                 line and point formulas spread over the lanes
-//   k_final_exp_team  one team: product of the Miller values, easy part f^((q^6-1)(q^2+1)), hard
-//                 part f^((q^4-q^2+1)/r) from f^x, f^(x^2), f^(x^3) and Frobenius maps, and the
-//                 test against 1
+//   k_final_exp_team  one team per block, one block per segment of the pairs: product of the
+//                 segment's Miller values, easy part f^((q^6-1)(q^2+1)), hard part
+//                 f^((q^4-q^2+1)/r) from f^x, f^(x^2), f^(x^3) and Frobenius maps, and the test
+//                 against 1 (one segment = multi_pairing; many = as many independent products)
 #include <algorithm>
 #include <map>
 #include <vector>
@@ -293,7 +298,7 @@ struct ExpLds {
     uint32_t flag[TEAM];
 };
 
-// the final exponentiation's exchange slots (one team per launch).  Namespace scope, so that the
+// the final exponentiation's exchange slots (one team per block).  Namespace scope, so that the
 // called helpers below address it as LDS directly; their operands go by value (registers), not by
 // reference (scratch)
 __shared__ ExpLds g_exp;
@@ -341,20 +346,25 @@ __device__ __noinline__ Fq2 team_pow_x(Fq2 a) {
     return r;
 }
 
-// One team: the product of the m Miller values, the final exponentiation (easy part
+// One team per block.  Block s takes the Miller values f[seg[s] .. seg[s + 1]) (seg null: the one
+// segment [0, m)); an empty segment is the identity.  The bounds are the block's own, so the
+// product loop's barriers stay uniform over the block.  The product of the segment's Miller
+// values, the final exponentiation (easy part
 // f^((q^6 - 1)(q^2 + 1)); hard part t^((q^4 - q^2 + 1) / r) = t^(l0 + l1 q + l2 q^2 + l3 q^3)
 // exactly, the l_i polynomials in x (Scott et al. 2009; identity asserted in
 // tools/pairing_consts.py): y0 = t^(q + q^2 + q^3), y1 = t^-1, y2 = t^(x^2 q^2), y3 = t^(-x q),
 // y4 = t^(-x - x^2 q), y5 = t^(-x^2), y6 = t^(-x^3 - x^3 q), and y0 y1^2 y2^6 y3^12 y4^18 y5^30
 // y6^36 by the addition chain), and the test against 1.  The one inversion gathers the element
 // on every lane.
-__global__ void __launch_bounds__(TEAM) k_final_exp_team(const Fq12* __restrict__ f, uint32_t m,
+__global__ void __launch_bounds__(TEAM) k_final_exp_team(const Fq12* __restrict__ f,
+                                                         const uint32_t* __restrict__ seg, uint32_t m,
                                                          Fq12* __restrict__ out, uint32_t* __restrict__ is_one) {
     ExpLds& L = g_exp;
     const TeamLane tl = team_lane();
     const int k = tl.k;
-    Fq2 acc = m ? w_coef(f[0], k) : (k == 0 ? f2_one() : f2_zero());
-    for (uint32_t i = 1; i < m; i++) acc = team_mul(acc, w_coef(f[i], k));
+    const uint32_t lo = seg ? seg[blockIdx.x] : 0, hi = seg ? seg[blockIdx.x + 1] : m;
+    Fq2 acc = hi > lo ? w_coef(f[lo], k) : (k == 0 ? f2_one() : f2_zero());
+    for (uint32_t i = lo + 1; i < hi; i++) acc = team_mul(acc, w_coef(f[i], k));
     // easy part; t is unitary from here on (its inverse is its conjugate)
     if (tl.pub) L.a[k] = acc;
     __syncthreads();
@@ -383,14 +393,14 @@ __global__ void __launch_bounds__(TEAM) k_final_exp_team(const Fq12* __restrict_
     t1 = team_mul(t1, y0);
     const Fq2 r = team_mul(t0, t1);
     if (tl.pub) {
-        set_w_coef(*out, k, r);
+        set_w_coef(out[blockIdx.x], k, r);
         L.flag[k] = f2_eq(r, k == 0 ? f2_one() : f2_zero()) ? 1u : 0u;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t all = 1;
         for (int j = 0; j < 6; j++) all &= L.flag[j];
-        *is_one = all;
+        is_one[blockIdx.x] = all;
     }
 }
 
@@ -398,21 +408,29 @@ __global__ void __launch_bounds__(TEAM) k_final_exp_team(const Fq12* __restrict_
 
 constexpr uint32_t VB_THREADS = 128;
 
-// block g < G: -sum of the witnesses of openings ord[gs[g] .. gs[g+1]); block G: sum of every
-// commitment and sum of every value
+// What one block of k_vb_sums / k_vb_pairs serves, built on the host.  A point's block (group = 1):
+// the openings ord[begin .. end) of one verify_batch that share an opening point.  A commitments'
+// block (group = 0): every opening [begin, end) of one verify_batch.  Block b makes pair b.
+struct VbBlock {
+    uint32_t begin, end, group;
+};
+
+// a point's block: -sum of the witnesses of its openings; a commitments' block: sum of every
+// commitment and sum of every value of its verify_batch
 __global__ void __launch_bounds__(VB_THREADS) k_vb_sums(const G1Affine* __restrict__ com, const G1Affine* __restrict__ wit,
                                                         const Fr* __restrict__ val, const uint32_t* __restrict__ ord,
-                                                        const uint32_t* __restrict__ gs, uint32_t G, uint32_t n,
-                                                        G1Xyzz* __restrict__ sums, Fr* __restrict__ vsum) {
+                                                        const VbBlock* __restrict__ blk, G1Xyzz* __restrict__ sums,
+                                                        Fr* __restrict__ vsum) {
     __shared__ G1Xyzz part[VB_THREADS];
     __shared__ Fr vpart[VB_THREADS];
     const uint32_t g = blockIdx.x, t = threadIdx.x;
+    const VbBlock d = blk[g];
     G1Xyzz acc = xyzz_inf();
     Fr vacc = Fr::zero();
-    if (g < G) {
-        for (uint32_t i = gs[g] + t; i < gs[g + 1]; i += VB_THREADS) acc = xyzz_add_affine(acc, wit[ord[i]]);
+    if (d.group) {
+        for (uint32_t i = d.begin + t; i < d.end; i += VB_THREADS) acc = xyzz_add_affine(acc, wit[ord[i]]);
     } else {
-        for (uint32_t i = t; i < n; i += VB_THREADS) {
+        for (uint32_t i = d.begin + t; i < d.end; i += VB_THREADS) {
             acc = xyzz_add_affine(acc, com[i]);
             vacc = add(vacc, val[i]);
         }
@@ -429,29 +447,31 @@ __global__ void __launch_bounds__(VB_THREADS) k_vb_sums(const G1Affine* __restri
     }
     if (t == 0) {
         G1Xyzz r = part[0];
-        if (g < G && !is_inf(r)) r.Y = neg(r.Y);  // -sum W
+        if (d.group && !is_inf(r)) r.Y = neg(r.Y);  // -sum W
         sums[g] = r;
-        if (g == G) *vsum = vpart[0];
+        if (!d.group) vsum[g] = vpart[0];
     }
 }
-
 
 // One block of VBP_THREADS per merged pair.  [k] of a fixed generator is the sum of the table
 // entries 2^i G of k's set bits: thread i sums the entries of bits [4i, 4i + 4), then an LDS tree
 // adds the 64 partial sums -- 4 + 6 dependent additions instead of one thread's ~128.
 constexpr uint32_t VBP_THREADS = 64;
 
+// block t (VbBlock t): zs[t] is a point's block's opening point, vsum[t] a commitments' block's sum
 __global__ void __launch_bounds__(VBP_THREADS) k_vb_pairs(const G1Xyzz* __restrict__ sums, const Fr* __restrict__ vsum,
-                                                          const Fr* __restrict__ zs, uint32_t G, G2Affine g2_alpha,
+                                                          const Fr* __restrict__ zs, const VbBlock* __restrict__ blk,
+                                                          uint32_t n_blk, G2Affine g2_alpha,
                                                           G1Affine* __restrict__ P, G2Affine* __restrict__ Q) {
     __shared__ G1Xyzz p1[VBP_THREADS];
     __shared__ G2Jac p2[VBP_THREADS];
     const uint32_t t = blockIdx.x, i = threadIdx.x;
-    if (t > G) return;
-    const Fr k = to_canonical(t == 0 ? *vsum : zs[t - 1]);
+    if (t >= n_blk) return;
+    const bool group = blk[t].group != 0;
+    const Fr k = to_canonical(group ? zs[t] : vsum[t]);
     const uint32_t word = k.v[i >> 3], b0 = 4 * i, sh = b0 & 31;
-    if (t == 0) {
-        // P_0 = sum C - (sum v) G1, Q_0 = G2
+    if (!group) {
+        // P = sum C - (sum v) G1, Q = G2
         G1Xyzz acc = xyzz_inf();
         for (uint32_t b = 0; b < 4; b++)
             if ((word >> (sh + b)) & 1)
@@ -464,8 +484,8 @@ __global__ void __launch_bounds__(VBP_THREADS) k_vb_pairs(const G1Xyzz* __restri
         }
         if (i == 0) {
             const G1Affine vg = xyzz_to_affine(p1[0]);
-            P[0] = xyzz_to_affine(xyzz_add_affine(sums[G], affine_neg(vg)));
-            Q[0] = g2_generator();
+            P[t] = xyzz_to_affine(xyzz_add_affine(sums[t], affine_neg(vg)));
+            Q[t] = g2_generator();
         }
     } else {
         // P_z = -sum W, Q_z = [alpha]G2 - z G2
@@ -482,7 +502,7 @@ __global__ void __launch_bounds__(VBP_THREADS) k_vb_pairs(const G1Xyzz* __restri
         if (i == 0) {
             G2Jac zg = p2[0];
             if (!f2_is_zero(zg.Z)) zg.Y = f2_neg(zg.Y);
-            P[t] = xyzz_to_affine(sums[t - 1]);
+            P[t] = xyzz_to_affine(sums[t]);
             Q[t] = g2j_to_affine(g2j_add_affine(zg, g2_alpha));
         }
     }
@@ -557,30 +577,137 @@ void fq12_to_abi(const Fq12& a, eon_fq12& out) {
     }
 }
 
-// product of the pairings of m device pairs -> Gt element and the is-one flag (host)
-Status pair_product(eon_ctx* ctx, const G1Affine* P, const G2Affine* Q, uint32_t m, Fq12* gt, bool* one) {
-    DevBuf f, res;
+// Products of the pairings of m device pairs cut into nseg segments by seg[0 .. nseg] (host;
+// ascending, seg[0] = 0, seg[nseg] = m) -> per segment the Gt element and the is-one flag (host
+// arrays of nseg, either may be null).  One Miller launch over all m pairs, one final
+// exponentiation block per segment.  seg null: the one segment [0, m).
+Status pair_product(eon_ctx* ctx, const G1Affine* P, const G2Affine* Q, uint32_t m, const uint32_t* seg, uint32_t nseg,
+                    Fq12* gt, uint32_t* one) {
+    if (!seg) nseg = 1;
+    if (nseg == 0) return Status::ok();
+    DevBuf f, res, dseg;
     PoolScope ps(ctx->pool, ctx->stream);
+    const size_t flags_at = (size_t)nseg * sizeof(Fq12);
     EON_HIP(ps.take(f, (size_t)std::max<uint32_t>(m, 1) * sizeof(Fq12)));
-    EON_HIP(ps.take(res, sizeof(Fq12) + 16));
+    EON_HIP(ps.take(res, flags_at + (size_t)nseg * 4));
+    if (seg) {
+        EON_HIP(ps.take(dseg, ((size_t)nseg + 1) * 4));
+        EON_HIP(hipMemcpyAsync(dseg.p, seg, ((size_t)nseg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
     ctx->prof.begin("k_miller_team", (uint64_t)m * (64 + 128 + 384), ctx->stream);
     if (m) hipLaunchKernelGGL(k_miller_team, dim3((m + 64 / TEAM - 1) / (64 / TEAM)), dim3(64), 0, ctx->stream, P, Q, m,
                               f.as<Fq12>());
     ctx->prof.end(ctx->stream);
-    ctx->prof.begin("k_final_exp_team", (uint64_t)m * 384 + 384, ctx->stream);
-    hipLaunchKernelGGL(k_final_exp_team, dim3(1), dim3(TEAM), 0, ctx->stream, f.as<Fq12>(), m, res.as<Fq12>(),
-                       reinterpret_cast<uint32_t*>(res.as<char>() + sizeof(Fq12)));
+    ctx->prof.begin("k_final_exp_team", (uint64_t)m * 384 + (uint64_t)nseg * 384, ctx->stream);
+    hipLaunchKernelGGL(k_final_exp_team, dim3(nseg), dim3(TEAM), 0, ctx->stream, f.as<Fq12>(),
+                       seg ? dseg.as<uint32_t>() : nullptr, m, res.as<Fq12>(),
+                       reinterpret_cast<uint32_t*>(res.as<char>() + flags_at));
     ctx->prof.end(ctx->stream);
     EON_HIP(hipGetLastError());
-    struct {
-        Fq12 v;
-        uint32_t flag;
-    } host;
-    EON_HIP(hipMemcpyAsync(&host.v, res.p, sizeof(Fq12), hipMemcpyDeviceToHost, ctx->stream));
-    EON_HIP(hipMemcpyAsync(&host.flag, res.as<char>() + sizeof(Fq12), 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (gt) EON_HIP(hipMemcpyAsync(gt, res.p, flags_at, hipMemcpyDeviceToHost, ctx->stream));
+    if (one) EON_HIP(hipMemcpyAsync(one, res.as<char>() + flags_at, (size_t)nseg * 4, hipMemcpyDeviceToHost, ctx->stream));
     EON_HIP(hipStreamSynchronize(ctx->stream));
-    if (gt) *gt = host.v;
-    if (one) *one = host.flag != 0;
+    return Status::ok();
+}
+
+// the offsets of an entry point's segments: ascending from 0; their end is the number of items
+Status check_segments(const uint64_t* seg, uint32_t nseg, uint64_t max_items, const char* what) {
+    if (seg[0] != 0) return Status::err(EON_E_ARG, "seg[0] must be 0");
+    for (uint32_t s = 0; s < nseg; s++)
+        if (seg[s + 1] < seg[s]) return Status::err(EON_E_ARG, "seg must be ascending");
+    if (seg[nseg] > max_items) return Status::err(EON_E_SHAPE, what);
+    return Status::ok();
+}
+
+// Segment s = openings [seg[s], seg[s + 1]) is one independent verify_batch: status[s] = 1 / 0 for
+// its product being the identity or not, EON_E_ARG (why[s] says what) when it holds something the
+// reference could not deserialise; such a segment gets no blocks and the others are still checked.
+// The openings are grouped by distinct point per segment (host: the points are few and small).
+Status verify_batch_segments(eon_ctx* ctx, const eon_g1_affine* commitments, const eon_g1_affine* witnesses,
+                             const eon_fr* values, const eon_fr* points, const uint64_t* seg, uint32_t nseg,
+                             const G2Affine& ga, int* status, std::string* why) {
+    const uint64_t n = seg[nseg];
+    std::vector<G1Affine> hc(n), hw(n);
+    std::vector<Fr> hv(n);
+    std::vector<uint32_t> ord(n), grp, pseg(nseg + 1, 0);
+    std::vector<VbBlock> blocks;
+    std::vector<Fr> zs;  // per block: a point's block's point
+    for (uint32_t s = 0; s < nseg; s++) {
+        const uint64_t lo = seg[s], hi = seg[s + 1];
+        std::map<std::vector<uint32_t>, uint32_t> gid;
+        std::vector<Fr> seg_zs;
+        grp.assign(hi - lo, 0);
+        Status bad = Status::ok();
+        for (uint64_t i = lo; i < hi && !bad.bad(); i++) {
+            if ((bad = g1_from_abi(commitments[i], hc[i])).bad()) break;
+            if ((bad = g1_from_abi(witnesses[i], hw[i])).bad()) break;
+            hv[i] = fr_from_abi(&values[i]);
+            const Fr z = fr_from_abi(&points[i]);
+            if (!fr_is_canonical(hv[i]) || !fr_is_canonical(z)) {
+                bad = Status::err(EON_E_ARG, "value or point is not a canonical Fr");
+                break;
+            }
+            std::vector<uint32_t> key(z.v, z.v + 8);
+            auto it = gid.find(key);
+            if (it == gid.end()) {
+                it = gid.emplace(key, (uint32_t)seg_zs.size()).first;
+                seg_zs.push_back(z);
+            }
+            grp[i - lo] = it->second;
+        }
+        status[s] = bad.bad() ? EON_E_ARG : 1;
+        if (why) why[s] = bad.msg;
+        if (!bad.bad() && hi > lo) {
+            const uint32_t G = (uint32_t)seg_zs.size();
+            std::vector<uint32_t> gs(G + 1, 0);
+            for (uint64_t i = lo; i < hi; i++) gs[grp[i - lo] + 1]++;
+            for (uint32_t g = 0; g < G; g++) gs[g + 1] += gs[g];
+            blocks.push_back({(uint32_t)lo, (uint32_t)hi, 0});
+            zs.push_back(Fr::zero());
+            for (uint32_t g = 0; g < G; g++) {
+                blocks.push_back({(uint32_t)lo + gs[g], (uint32_t)lo + gs[g + 1], 1});
+                zs.push_back(seg_zs[g]);
+            }
+            for (uint64_t i = lo; i < hi; i++) ord[lo + gs[grp[i - lo]]++] = (uint32_t)i;
+        }
+        pseg[s + 1] = (uint32_t)blocks.size();
+    }
+    const uint32_t B = (uint32_t)blocks.size();
+    if (B == 0) return Status::ok();  // nothing but empty and malformed segments
+    DevBuf dc, dw, dv, dord, dblk, dz, dsums, dvsum, dP, dQ;
+    PoolScope ps(ctx->pool, ctx->stream);
+    EON_HIP(ps.take(dc, n * sizeof(G1Affine)));
+    EON_HIP(ps.take(dw, n * sizeof(G1Affine)));
+    EON_HIP(ps.take(dv, n * sizeof(Fr)));
+    EON_HIP(ps.take(dord, n * 4));
+    EON_HIP(ps.take(dblk, B * sizeof(VbBlock)));
+    EON_HIP(ps.take(dz, B * sizeof(Fr)));
+    EON_HIP(ps.take(dsums, B * sizeof(G1Xyzz)));
+    EON_HIP(ps.take(dvsum, B * sizeof(Fr)));
+    EON_HIP(ps.take(dP, B * sizeof(G1Affine)));
+    EON_HIP(ps.take(dQ, B * sizeof(G2Affine)));
+    hipStream_t st = ctx->stream;
+    EON_HIP(hipMemcpyAsync(dc.p, hc.data(), n * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+    EON_HIP(hipMemcpyAsync(dw.p, hw.data(), n * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+    EON_HIP(hipMemcpyAsync(dv.p, hv.data(), n * sizeof(Fr), hipMemcpyHostToDevice, st));
+    EON_HIP(hipMemcpyAsync(dord.p, ord.data(), n * 4, hipMemcpyHostToDevice, st));
+    EON_HIP(hipMemcpyAsync(dblk.p, blocks.data(), B * sizeof(VbBlock), hipMemcpyHostToDevice, st));
+    EON_HIP(hipMemcpyAsync(dz.p, zs.data(), B * sizeof(Fr), hipMemcpyHostToDevice, st));
+    // algorithmic bytes: each opening's commitment, witness, value and point read once
+    ctx->prof.begin("k_vb_sums", n * (64 + 64 + 32 + 32), st);
+    hipLaunchKernelGGL(k_vb_sums, dim3(B), dim3(VB_THREADS), 0, st, dc.as<G1Affine>(), dw.as<G1Affine>(), dv.as<Fr>(),
+                       dord.as<uint32_t>(), dblk.as<VbBlock>(), dsums.as<G1Xyzz>(), dvsum.as<Fr>());
+    ctx->prof.end(st);
+    ctx->prof.begin("k_vb_pairs", (uint64_t)B * (96 + 192), st);
+    hipLaunchKernelGGL(k_vb_pairs, dim3(B), dim3(VBP_THREADS), 0, st, dsums.as<G1Xyzz>(), dvsum.as<Fr>(), dz.as<Fr>(),
+                       dblk.as<VbBlock>(), B, ga, dP.as<G1Affine>(), dQ.as<G2Affine>());
+    ctx->prof.end(st);
+    EON_HIP(hipGetLastError());
+    std::vector<uint32_t> one(nseg, 0);
+    EON_TRY(pair_product(ctx, dP.as<G1Affine>(), dQ.as<G2Affine>(), B, nseg == 1 ? nullptr : pseg.data(), nseg, nullptr,
+                         one.data()));
+    for (uint32_t s = 0; s < nseg; s++)
+        if (status[s] != EON_E_ARG) status[s] = one[s] ? 1 : 0;
     return Status::ok();
 }
 
@@ -639,8 +766,44 @@ int eon_multi_pairing(eon_ctx* ctx, const eon_g1_affine* p, const eon_g2_affine*
             EON_HIP(hipMemcpyAsync(dq.p, hq.data(), n * sizeof(G2Affine), hipMemcpyHostToDevice, ctx->stream));
         }
         Fq12 gt;
-        EON_TRY(pair_product(ctx, dp.as<G1Affine>(), dq.as<G2Affine>(), (uint32_t)n, &gt, nullptr));
+        EON_TRY(pair_product(ctx, dp.as<G1Affine>(), dq.as<G2Affine>(), (uint32_t)n, nullptr, 1, &gt, nullptr));
         fq12_to_abi(gt, *out);
+        return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+int eon_multi_pairing_many(eon_ctx* ctx, const eon_g1_affine* p, const eon_g2_affine* q, const uint64_t* seg,
+                           uint32_t nseg, eon_fq12* out) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (nseg == 0) return Status::ok();
+        if (!out || !seg) return Status::err(EON_E_ARG, "null argument");
+        if (nseg > (1u << 24)) return Status::err(EON_E_SHAPE, "at most 2^24 segments");
+        EON_TRY(check_segments(seg, nseg, 1u << 24, "at most 2^24 pairs"));
+        const uint64_t n = seg[nseg];
+        if (n && (!p || !q)) return Status::err(EON_E_ARG, "null argument");
+        std::vector<G1Affine> hp(n);
+        std::vector<G2Affine> hq(n);
+        for (uint64_t i = 0; i < n; i++) {
+            EON_TRY(g1_from_abi(p[i], hp[i]));
+            EON_TRY(g2_from_abi(q[i], hq[i]));
+        }
+        std::vector<uint32_t> seg32(seg, seg + nseg + 1);
+        DevBuf dp, dq;
+        PoolScope ps(ctx->pool, ctx->stream);
+        EON_HIP(ps.take(dp, std::max<uint64_t>(n, 1) * sizeof(G1Affine)));
+        EON_HIP(ps.take(dq, std::max<uint64_t>(n, 1) * sizeof(G2Affine)));
+        if (n) {
+            EON_HIP(hipMemcpyAsync(dp.p, hp.data(), n * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+            EON_HIP(hipMemcpyAsync(dq.p, hq.data(), n * sizeof(G2Affine), hipMemcpyHostToDevice, ctx->stream));
+        }
+        std::vector<Fq12> gt(nseg);
+        EON_TRY(pair_product(ctx, dp.as<G1Affine>(), dq.as<G2Affine>(), (uint32_t)n, seg32.data(), nseg, gt.data(),
+                             nullptr));
+        for (uint32_t i = 0; i < nseg; i++) fq12_to_abi(gt[i], out[i]);
         return Status::ok();
     }();
     return finish(ctx, s);
@@ -663,68 +826,34 @@ int eon_kzg_verify_batch(eon_ctx* ctx, const eon_g1_affine* commitments, const e
         }
         G2Affine ga;
         EON_TRY(g2_from_abi(*g2_alpha, ga));
-        std::vector<G1Affine> hc(n), hw(n);
-        std::vector<Fr> hv(n);
-        // group the openings by point (host: the points are few and small)
-        std::map<std::vector<uint32_t>, uint32_t> gid;
-        std::vector<Fr> zs;
-        std::vector<uint32_t> grp(n);
-        for (uint64_t i = 0; i < n; i++) {
-            EON_TRY(g1_from_abi(commitments[i], hc[i]));
-            EON_TRY(g1_from_abi(witnesses[i], hw[i]));
-            hv[i] = fr_from_abi(&values[i]);
-            const Fr z = fr_from_abi(&points[i]);
-            if (!fr_is_canonical(hv[i]) || !fr_is_canonical(z)) return Status::err(EON_E_ARG, "value or point is not a canonical Fr");
-            std::vector<uint32_t> key(z.v, z.v + 8);
-            auto it = gid.find(key);
-            if (it == gid.end()) {
-                it = gid.emplace(key, (uint32_t)zs.size()).first;
-                zs.push_back(z);
-            }
-            grp[i] = it->second;
-        }
-        const uint32_t G = (uint32_t)zs.size();
-        std::vector<uint32_t> gs(G + 1, 0), ord(n);
-        for (uint64_t i = 0; i < n; i++) gs[grp[i] + 1]++;
-        for (uint32_t g = 0; g < G; g++) gs[g + 1] += gs[g];
-        {
-            std::vector<uint32_t> fill(gs.begin(), gs.end() - 1);
-            for (uint64_t i = 0; i < n; i++) ord[fill[grp[i]]++] = (uint32_t)i;
-        }
-        DevBuf dc, dw, dv, dord, dgs, dz, dsums, dvsum, dP, dQ;
-        PoolScope ps(ctx->pool, ctx->stream);
-        EON_HIP(ps.take(dc, n * sizeof(G1Affine)));
-        EON_HIP(ps.take(dw, n * sizeof(G1Affine)));
-        EON_HIP(ps.take(dv, n * sizeof(Fr)));
-        EON_HIP(ps.take(dord, n * 4));
-        EON_HIP(ps.take(dgs, (G + 1) * 4));
-        EON_HIP(ps.take(dz, G * sizeof(Fr)));
-        EON_HIP(ps.take(dsums, (G + 1) * sizeof(G1Xyzz)));
-        EON_HIP(ps.take(dvsum, sizeof(Fr)));
-        EON_HIP(ps.take(dP, (G + 1) * sizeof(G1Affine)));
-        EON_HIP(ps.take(dQ, (G + 1) * sizeof(G2Affine)));
-        hipStream_t st = ctx->stream;
-        EON_HIP(hipMemcpyAsync(dc.p, hc.data(), n * sizeof(G1Affine), hipMemcpyHostToDevice, st));
-        EON_HIP(hipMemcpyAsync(dw.p, hw.data(), n * sizeof(G1Affine), hipMemcpyHostToDevice, st));
-        EON_HIP(hipMemcpyAsync(dv.p, hv.data(), n * sizeof(Fr), hipMemcpyHostToDevice, st));
-        EON_HIP(hipMemcpyAsync(dord.p, ord.data(), n * 4, hipMemcpyHostToDevice, st));
-        EON_HIP(hipMemcpyAsync(dgs.p, gs.data(), (G + 1) * 4, hipMemcpyHostToDevice, st));
-        EON_HIP(hipMemcpyAsync(dz.p, zs.data(), G * sizeof(Fr), hipMemcpyHostToDevice, st));
-        // algorithmic bytes: each opening's commitment, witness, value and point read once
-        ctx->prof.begin("k_vb_sums", n * (64 + 64 + 32 + 32), st);
-        hipLaunchKernelGGL(k_vb_sums, dim3(G + 1), dim3(VB_THREADS), 0, st, dc.as<G1Affine>(), dw.as<G1Affine>(),
-                           dv.as<Fr>(), dord.as<uint32_t>(), dgs.as<uint32_t>(), G, (uint32_t)n, dsums.as<G1Xyzz>(),
-                           dvsum.as<Fr>());
-        ctx->prof.end(st);
-        ctx->prof.begin("k_vb_pairs", (uint64_t)(G + 1) * (96 + 192), st);
-        hipLaunchKernelGGL(k_vb_pairs, dim3(G + 1), dim3(VBP_THREADS), 0, st, dsums.as<G1Xyzz>(), dvsum.as<Fr>(),
-                           dz.as<Fr>(), G, ga, dP.as<G1Affine>(), dQ.as<G2Affine>());
-        ctx->prof.end(st);
-        EON_HIP(hipGetLastError());
-        bool one = false;
-        EON_TRY(pair_product(ctx, dP.as<G1Affine>(), dQ.as<G2Affine>(), G + 1, nullptr, &one));
-        *ok = one ? 1 : 0;
+        // the one-segment case of eon_kzg_verify_batch_many
+        const uint64_t seg[2] = {0, n};
+        int status = 0;
+        std::string why;
+        EON_TRY(verify_batch_segments(ctx, commitments, witnesses, values, points, seg, 1, ga, &status, &why));
+        if (status == EON_E_ARG) return Status::err(EON_E_ARG, why);
+        *ok = status;
         return Status::ok();
+    }();
+    return finish(ctx, s);
+}
+
+int eon_kzg_verify_batch_many(eon_ctx* ctx, const eon_g1_affine* commitments, const eon_g1_affine* witnesses,
+                              const eon_fr* values, const eon_fr* points, const uint64_t* seg, uint32_t nseg,
+                              const eon_g2_affine* g2_alpha, int* status) {
+    if (!ctx) return EON_E_ARG;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (hipSetDevice(ctx->device) != hipSuccess) return EON_E_DEVICE;
+    Status s = [&]() -> Status {
+        if (nseg == 0) return Status::ok();
+        if (!status || !seg || !g2_alpha) return Status::err(EON_E_ARG, "null argument");
+        if (nseg > (1u << 24)) return Status::err(EON_E_SHAPE, "at most 2^24 segments");
+        EON_TRY(check_segments(seg, nseg, 1u << 26, "at most 2^26 openings"));
+        if (seg[nseg] && (!commitments || !witnesses || !values || !points))
+            return Status::err(EON_E_ARG, "null argument");
+        G2Affine ga;
+        EON_TRY(g2_from_abi(*g2_alpha, ga));
+        return verify_batch_segments(ctx, commitments, witnesses, values, points, seg, nseg, ga, status, nullptr);
     }();
     return finish(ctx, s);
 }

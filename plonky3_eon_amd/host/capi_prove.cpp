@@ -18,6 +18,7 @@ struct eon_kzg_pcs {
     eon_host::Fr gamma = eon_host::Fr::zero(), delta = eon_host::Fr::zero();
     bool have_last = false;  // of the last batched prove / verify
     eon_host::Fr last_gamma = eon_host::Fr::zero(), last_delta = eon_host::Fr::zero();
+    std::vector<eon_host::VerifyOutcome> many;  // of the last eon_verify_air_many[_fs]
 };
 
 struct eon_preprocessed {
@@ -107,7 +108,7 @@ bool proof_arrays_ok(const eon_proof* out) {
 
 extern "C" {
 
-uint32_t eon_prove_abi_version(void) { return 10; }
+uint32_t eon_prove_abi_version(void) { return 11; }
 
 int eon_kzg_pcs_create(eon_ctx* ctx, uint64_t max_degree, const eon_fr* srs_alpha, eon_kzg_pcs** out) {
     if (!ctx || !srs_alpha || !out) return EON_E_ARG;
@@ -561,6 +562,125 @@ int eon_verify_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_p
     });
     if (rc == EON_OK) pcs->last_error = detail;
     return rc;
+}
+
+}  // extern "C"
+
+namespace {
+
+// eon_verify_air_many[_fs]: the n inputs from the C arrays, eon_host::verify_many, the verdicts out
+// and the outcomes kept for eon_verify_many_detail / _opening_challenges.  `fill(i, in)` sets what
+// differs between the two entry points.
+template <class Fill>
+int verify_many_c(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proofs, uint32_t n,
+                  const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                  const eon_g1_affine* vk_commitment, const std::vector<eon_host::DuplexChallenger*>& challengers,
+                  int* results, Fill fill) {
+    pcs->many.clear();
+    std::string first;
+    const int rc = guarded(pcs, [&] {
+        using namespace eon_host;
+        std::vector<VerifyInputs> ins(n);
+        for (uint32_t i = 0; i < n; i++) {
+            VerifyInputs& in = ins[i];
+            in.prog = prog;
+            in.proof = &proofs[i];
+            in.publics = n_public ? publics + (size_t)i * n_public : nullptr;
+            in.n_public = n_public;
+            in.vk_width = vk_width;
+            in.vk_degree_bits = vk_degree_bits;
+            in.vk_commitment = vk_commitment;
+            in.batched = pcs->opening == EON_OPENING_BATCHED;
+            fill(i, in);
+        }
+        std::vector<VerifyOutcome> outs = verify_many(*pcs->pcs, ins, challengers);
+        for (uint32_t i = 0; i < n; i++) {
+            results[i] = outs[i].verdict;
+            if (outs[i].verdict != EON_VERIFY_OK && first.empty())
+                first = "proof " + std::to_string(i) + ": " + outs[i].detail;
+        }
+        pcs->many = std::move(outs);
+    });
+    if (rc == EON_OK) pcs->last_error = first;  // why the first rejected proof was rejected
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eon_verify_air_many(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proofs, uint32_t n,
+                        const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                        const eon_g1_affine* vk_commitment, const eon_fr* challenges, uint32_t n_challenges,
+                        const eon_fr* alphas, const eon_fr* zetas, const eon_fr* gammas, const eon_fr* deltas,
+                        int* results) {
+    if (!pcs || !pcs->pcs) return EON_E_ARG;
+    if (n == 0) {
+        pcs->many.clear();
+        return EON_OK;
+    }
+    if (!prog || !proofs || !alphas || !zetas || !results || (n_public && !publics) || (n_challenges && !challenges))
+        return EON_E_ARG;
+    const bool batched = pcs->opening == EON_OPENING_BATCHED;
+    if (batched && ((!gammas && !pcs->have_gamma) || (!deltas && !pcs->have_delta))) {
+        pcs->last_error = "the batched opening without a challenger needs gamma and delta (the arrays, or "
+                          "eon_kzg_pcs_set_opening_challenges)";
+        return EON_E_ARG;
+    }
+    return verify_many_c(pcs, prog, proofs, n, publics, n_public, vk_width, vk_degree_bits, vk_commitment, {}, results,
+                         [&](uint32_t i, eon_host::VerifyInputs& in) {
+                             using eon_host::Fr;
+                             in.challenges = n_challenges ? challenges + (size_t)i * n_challenges : nullptr;
+                             in.n_challenges = n_challenges;
+                             in.alpha = Fr::from_abi(alphas[i]);
+                             in.zeta = Fr::from_abi(zetas[i]);
+                             in.gamma = gammas ? Fr::from_abi(gammas[i]) : pcs->gamma;
+                             in.delta = deltas ? Fr::from_abi(deltas[i]) : pcs->delta;
+                         });
+}
+
+int eon_verify_air_many_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_proof_lk* proofs, uint32_t n,
+                           const eon_fr* publics, uint32_t n_public, uint32_t vk_width, uint32_t vk_degree_bits,
+                           const eon_g1_affine* vk_commitment, eon_challenger* const* challengers, int* results,
+                           eon_fr* challenges_out, eon_fr* alphas_out, eon_fr* zetas_out) {
+    if (!pcs || !pcs->pcs) return EON_E_ARG;
+    if (n == 0) {
+        pcs->many.clear();
+        return EON_OK;
+    }
+    if (!prog || !proofs || !challengers || !results || (n_public && !publics)) return EON_E_ARG;
+    std::vector<eon_host::DuplexChallenger*> chs(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!challengers[i]) return EON_E_ARG;
+        for (uint32_t j = 0; j < i; j++)
+            if (challengers[j] == challengers[i]) return EON_E_ARG;  // one transcript per proof
+        chs[i] = &challengers[i]->ch;
+    }
+    const int rc = verify_many_c(pcs, prog, proofs, n, publics, n_public, vk_width, vk_degree_bits, vk_commitment, chs,
+                                 results, [](uint32_t, eon_host::VerifyInputs&) {});
+    if (rc != EON_OK) return rc;
+    const uint32_t n_ch = eon_air_program_num_challenges(prog);
+    for (uint32_t i = 0; i < n; i++) {
+        const eon_host::VerifyOutcome& o = pcs->many[i];
+        if (o.verdict == EON_VERIFY_INVALID_PROOF_SHAPE) continue;  // rejected before the transcript
+        if (challenges_out)
+            for (size_t j = 0; j < o.challenges.size(); j++) challenges_out[(size_t)i * n_ch + j] = o.challenges[j].abi();
+        if (alphas_out) alphas_out[i] = o.alpha.abi();
+        if (zetas_out) zetas_out[i] = o.zeta.abi();
+    }
+    return rc;
+}
+
+const char* eon_verify_many_detail(const eon_kzg_pcs* pcs, uint32_t i) {
+    if (!pcs || i >= pcs->many.size()) return nullptr;
+    return pcs->many[i].detail.c_str();
+}
+
+int eon_verify_many_opening_challenges(const eon_kzg_pcs* pcs, uint32_t i, eon_fr* gamma, eon_fr* delta) {
+    if (!pcs || !gamma || !delta || i >= pcs->many.size()) return EON_E_ARG;
+    *gamma = pcs->many[i].gamma.abi();
+    *delta = pcs->many[i].delta.abi();
+    return EON_OK;
 }
 
 }  // extern "C"

@@ -120,6 +120,7 @@ class KzgPcs {
     eon_ctx* ctx() const { return ctx_; }
     Domain natural_domain_for_degree(uint64_t degree) const;  // pcs.rs:218-221
     void ensure_supported(uint64_t degree) const;             // params.rs:164-173
+    uint64_t max_degree() const { return max_degree_; }
 
     // pcs.rs:223-265: coset_idft_batch of each matrix, one commitment per column
     void commit(std::vector<std::pair<Domain, DeviceMatrix>> evaluations,

@@ -3,7 +3,11 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <cstdio>
 #include <cstring>
+#include <exception>
+#include <thread>
 
 #include "verify_host.h"
 
@@ -11,390 +15,225 @@ namespace eon_host {
 
 namespace {
 
-// A G1 point as the reference's deserialisation admits it: the identity (0, 0), or canonical
-// coordinates with y^2 = x^3 + 3 (Montgomery residues; G1 has cofactor 1, so on the curve is in the
-// group).  The batched verify folds commitments through an MSM before the pairing check sees them,
-// so the raw points are tested here.
-struct Fq4 {
-    uint64_t l[4];
-};
-constexpr uint64_t FQ_P[4] = {0x3c208c16d87cfd47ull, 0x97816a916871ca8dull, 0xb85045b68181585dull,
-                              0x30644e72e131a029ull};
-// 3 * 2^256 mod q: the curve's b in Montgomery form
-constexpr uint64_t FQ_THREE[4] = {0x7a17caa950ad28d7ull, 0x1f6ac17ae15521b9ull, 0x334bea4e696bd284ull,
-                                  0x2a1f6744ce179d8eull};
-
-bool fq_geq_p(const Fq4& a) {
-    for (int i = 3; i >= 0; i--)
-        if (a.l[i] != FQ_P[i]) return a.l[i] > FQ_P[i];
-    return true;
+void reject(Prepared& p, int v, const std::string& why) {
+    p.out.verdict = v;
+    p.out.detail = why;
+    p.done = true;
 }
 
-// a b 2^-256 mod q, canonical (CIOS; a, b < q)
-Fq4 fq_mul(const Fq4& a, const Fq4& b) {
-    typedef unsigned __int128 u128;
-    uint64_t inv = 1;  // -q^-1 mod 2^64 by Newton iteration
-    for (int i = 0; i < 6; i++) inv *= 2 - FQ_P[0] * inv;
-    inv = ~inv + 1;
-    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < 4; i++) {
-        u128 c = 0;
-        for (int j = 0; j < 4; j++) {
-            c += (u128)a.l[j] * b.l[i] + t[j];
-            t[j] = (uint64_t)c;
-            c >>= 64;
-        }
-        c += t[4];
-        t[4] = (uint64_t)c;
-        t[5] = (uint64_t)(c >> 64);
-        const uint64_t m = t[0] * inv;
-        c = (u128)m * FQ_P[0] + t[0];
-        c >>= 64;
-        for (int j = 1; j < 4; j++) {
-            c += (u128)m * FQ_P[j] + t[j];
-            t[j - 1] = (uint64_t)c;
-            c >>= 64;
-        }
-        c += t[4];
-        t[3] = (uint64_t)c;
-        t[4] = t[5] + (uint64_t)(c >> 64);
-    }
-    Fq4 r{{t[0], t[1], t[2], t[3]}};
-    if (t[4] || fq_geq_p(r)) {
-        uint64_t borrow = 0;
-        for (int i = 0; i < 4; i++) {
-            const u128 x = (u128)r.l[i] - FQ_P[i] - borrow;
-            r.l[i] = (uint64_t)x;
-            borrow = (uint64_t)(x >> 64) & 1;
-        }
-    }
-    return r;
-}
-
-bool g1_valid(const eon_g1_affine& p) {
-    typedef unsigned __int128 u128;
-    Fq4 x, y;
-    for (int i = 0; i < 4; i++) x.l[i] = p.x[i], y.l[i] = p.y[i];
-    if (!(x.l[0] | x.l[1] | x.l[2] | x.l[3] | y.l[0] | y.l[1] | y.l[2] | y.l[3])) return true;
-    if (fq_geq_p(x) || fq_geq_p(y)) return false;
-    Fq4 rhs = fq_mul(fq_mul(x, x), x);
-    u128 c = 0;
-    for (int i = 0; i < 4; i++) {  // + 3: below 2q < 2^255
-        c += (u128)rhs.l[i] + FQ_THREE[i];
-        rhs.l[i] = (uint64_t)c;
-        c >>= 64;
-    }
-    if (fq_geq_p(rhs)) {
-        uint64_t borrow = 0;
-        for (int i = 0; i < 4; i++) {
-            const u128 d = (u128)rhs.l[i] - FQ_P[i] - borrow;
-            rhs.l[i] = (uint64_t)d;
-            borrow = (uint64_t)(d >> 64) & 1;
-        }
-    }
-    const Fq4 lhs = fq_mul(y, y);
-    return lhs.l[0] == rhs.l[0] && lhs.l[1] == rhs.l[1] && lhs.l[2] == rhs.l[2] && lhs.l[3] == rhs.l[3];
-}
-
-VerifyOutcome verdict(VerifyOutcome o, int v, const std::string& why) {
-    o.verdict = v;
-    o.detail = why;
-    return o;
-}
-
-}  // namespace
-
-VerifyOutcome verify(KzgPcs& pcs, const VerifyInputs& in, DuplexChallenger* challenger) {
-    eon_ctx* ctx = pcs.ctx();
-    if (!in.prog || !in.proof) throw Error(EON_E_ARG, "null program or proof");
-    if (in.n_public && !in.publics) throw Error(EON_E_ARG, "null public values");
-    const eon_proof_lk& lk = *in.proof;
-    const eon_proof_pp& pp = lk.pp;
-    const eon_proof& b = pp.base;
-    if (!b.trace_commit || !b.quotient_commit || !b.trace_opened || !b.trace_witnesses || !b.quotient_opened ||
-        !b.quotient_witnesses)
-        throw Error(EON_E_ARG, "null trace or quotient arrays in the proof");
+ProgShape prog_shape(eon_ctx* ctx, const eon_air_program* prog) {
+    if (!prog) throw Error(EON_E_ARG, "null program or proof");
     eon_air_program_stats st{};
-    check(ctx, eon_air_program_info(in.prog, &st), "eon_air_program_info");
-    if (in.n_public != st.num_public_values)
-        throw Error(EON_E_SHAPE, "public value count differs from the program's");
-    const uint32_t width = st.width;
-    const uint32_t prog_pre_width = eon_air_program_preprocessed_width(in.prog);
-    const uint32_t perm_width = eon_air_program_permutation_width(in.prog);
-    const uint32_t n_challenges = eon_air_program_num_challenges(in.prog);
-    const uint32_t log_qd = eon_air_program_log_quotient_degree(in.prog, 0);  // :296-304
-    const uint32_t num_chunks = 1u << log_qd;
-    const uint32_t log_n = b.degree_bits;
-    if (log_n + log_qd > Fr::TWO_ADICITY)  // the reference's two_adic_generator panics
-        throw Error(EON_E_SHAPE, "degree_bits " + std::to_string(log_n) + " + log_quotient_degree exceeds the field's "
-                                 "two-adicity");
-    VerifyOutcome out;
+    check(ctx, eon_air_program_info(prog, &st), "eon_air_program_info");
+    return {st.width,
+            st.num_public_values,
+            eon_air_program_preprocessed_width(prog),
+            eon_air_program_permutation_width(prog),
+            eon_air_program_num_challenges(prog),
+            eon_air_program_log_quotient_degree(prog, 0)};  // :296-304
+}
 
-    // ---- 1. shapes ------------------------------------------------------------------------------
-    // process_preprocessed_trace (:165-225): the expected width is the key's, else the AIR's; the
-    // proof carries preprocessed openings exactly when it is nonzero; a width needs a key and a key's
-    // width is the width.  (The array widths themselves are the caller's: C arrays carry no length.)
-    const bool has_vk = in.vk_commitment != nullptr;
-    const uint32_t pre_width = has_vk ? in.vk_width : prog_pre_width;
-    const bool proof_has_pre = pp.preprocessed_opened != nullptr;
-    if ((pre_width > 0) != proof_has_pre)
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE,
-                       "the verifier expects " + std::to_string(pre_width) + " preprocessed columns and the proof " +
-                           (proof_has_pre ? "opens some" : "opens none"));
-    if (pre_width > 0 && !has_vk)
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE,
-                       "the AIR has preprocessed columns but no verifier key was given");
-    if (pre_width > 0 && !pp.preprocessed_witnesses)
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE, "preprocessed openings without witnesses");
-    // the program reads exactly its own preprocessed columns (the reference's AIR would index past
-    // the opened row, or ignore it)
-    if (pre_width != prog_pre_width)
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE,
-                       "the verifier key's width " + std::to_string(pre_width) + " differs from the AIR's " +
-                           std::to_string(prog_pre_width));
-    if (has_vk && pre_width > 0 && in.vk_degree_bits != log_n)  // :272-277
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE,
-                       "the verifier key's degree_bits " + std::to_string(in.vk_degree_bits) +
-                           " differs from the proof's " + std::to_string(log_n));
-    // :330-352: the permutation commitment and both opened rows, all or none; and all exactly when
-    // the program has lookups
-    const bool has_perm_commit = lk.permutation_commit != nullptr;
-    const bool has_perm_opened = lk.permutation_opened != nullptr;
-    if (has_perm_commit != has_perm_opened || (has_perm_commit && !lk.permutation_witnesses))
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE, "permutation commitment and openings must come together");
-    if (has_perm_commit != (perm_width > 0))
-        return verdict(out, EON_VERIFY_INVALID_PROOF_SHAPE,
-                       perm_width > 0 ? "the AIR has lookups but the proof has no permutation part"
-                                      : "the proof has a permutation part but the AIR has no lookups");
-    // the given challenges are the program's (after the shapes: a proof without its permutation part
-    // is a verdict, whatever came with it)
-    if (!challenger && in.n_challenges != n_challenges)
-        throw Error(EON_E_SHAPE, "challenge count differs from the program's");
-    if (!challenger && n_challenges && !in.challenges) throw Error(EON_E_ARG, "null permutation challenges");
+// batched mode: delta^i C_i and delta^i W_i of the K claims, one variable-base column MSM
+void scale_claims(eon_ctx* ctx, Prepared& p) {
+    const size_t K = p.vs.size(), cols = 2 * K, n_pts = p.pts.size();
+    std::vector<eon_g1_affine> scaled(cols);
+    eon_msm_bases* bases = nullptr;
+    check(ctx, eon_msm_bases_create(ctx, p.pts.data(), n_pts, 0, &bases), "eon_msm_bases_create");
+    const int mrc = eon_msm_g1_columns(ctx, bases, p.scal.data(), n_pts, (uint32_t)cols, scaled.data());
+    eon_msm_bases_destroy(bases);
+    check(ctx, mrc, "eon_msm_g1_columns");
+    p.cs.assign(scaled.begin(), scaled.begin() + K);
+    p.ws.assign(scaled.begin() + K, scaled.end());
+}
 
-    // ---- 2. the transcript (:355-397) -----------------------------------------------------------
-    out.alpha = in.alpha;
-    out.zeta = in.zeta;
-    out.challenges.resize(has_perm_commit ? n_challenges : 0);
-    if (challenger) {
-        challenger->observe(fr_from_u64(log_n));      // degree_bits
-        challenger->observe(fr_from_u64(log_n));      // degree_bits - is_zk
-        challenger->observe(fr_from_u64(pre_width));  // preprocessed width
-        challenger->observe_g1(b.trace_commit, width);
-        if (pre_width > 0) challenger->observe_g1(in.vk_commitment, pre_width);  // the key's, never the proof's
-        for (uint32_t i = 0; i < in.n_public; i++) {
-            const Fr v = Fr::from_abi(in.publics[i]);
-            if (!fr_is_canonical(v)) throw Error(EON_E_ARG, "public value is not a canonical Fr");
-            challenger->observe(v);
-        }
-        if (has_perm_commit) {
-            for (auto& c : out.challenges) c = challenger->sample();
-            challenger->observe_g1(lk.permutation_commit, perm_width);
-        }
-        out.alpha = challenger->sample();
-        challenger->observe_g1(b.quotient_commit, num_chunks);
-        out.zeta = challenger->sample();
-    } else {
-        for (uint32_t i = 0; i < (uint32_t)out.challenges.size(); i++) out.challenges[i] = Fr::from_abi(in.challenges[i]);
-        if (!fr_is_canonical(out.alpha) || !fr_is_canonical(out.zeta))
-            throw Error(EON_E_ARG, "alpha or zeta is not a canonical Fr");
+// one proof's verify_batch alone: 1 / 0, or EON_E_ARG with the library's message in *why
+int openings_alone(KzgPcs& pcs, const Prepared& p, std::string* why) {
+    eon_ctx* ctx = pcs.ctx();
+    int ok = 0;
+    const int rc = eon_kzg_verify_batch(ctx, p.cs.data(), p.ws.data(), p.vs.data(), p.zs.data(), p.cs.size(),
+                                        &pcs.g2_alpha(), &ok);
+    // a commitment or witness that is no curve point, or an opened value that is no canonical
+    // Fr, cannot come out of the reference's deserialisation: not an opening
+    if (rc == EON_E_ARG) {
+        const char* msg = eon_last_error(ctx);
+        *why = msg ? msg : "invalid argument";
+        return EON_E_ARG;
     }
-    const Fr zeta = out.zeta;
-    const Fr zeta_next = pcs.natural_domain_for_degree(1ull << log_n).next_point(zeta);
+    check(ctx, rc, "eon_kzg_verify_batch");
+    return ok;
+}
 
-    // ---- 3. KzgPcs::verify (kzg/src/pcs.rs:337-401) ---------------------------------------------
-    // ensure_supported per domain: the trace domain and the chunk domains all have 2^log_n points
-    try {
-        pcs.ensure_supported((1ull << log_n) - 1);
-    } catch (const Error& e) {
-        if (e.code != EON_E_DEGREE_TOO_LARGE) throw;
-        return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT, std::string("KzgError::DegreeTooLarge: ") + e.what());
-    }
-    if (in.batched) {
-        // The batched opening (EON_OPENING_BATCHED; not the reference's proof format): claim i =
-        // (matrix, point) in the round order carries ONE witness W_i.  With C_i = sum_j gamma^j C_(m,j)
-        // and v_i = sum_j gamma^j v_(i,j), the K claims go to ONE eon_kzg_verify_batch as
-        // (delta^i C_i, delta^i W_i, delta^i v_i, z_i): prod_i e(delta^i (C_i - v_i G1), G2)
-        // e(-delta^i W_i, g2_alpha - z_i G2) = 1.  The weights are what makes the product a sound
-        // batch check (the per-column mode keeps the reference's unweighted one).
-        struct Claim {
-            const eon_g1_affine* commit;
-            const eon_fr* values;
-            const eon_g1_affine* witness;
-            uint32_t w;
-            Fr z;
-        };
-        std::vector<Claim> claims;
-        auto matrix = [&](const eon_g1_affine* commit, const eon_fr* opened, const eon_g1_affine* wit, uint32_t w) {
-            claims.push_back({commit, opened, wit, w, zeta});
-            claims.push_back({commit, opened + w, wit + 1, w, zeta_next});
-        };
-        matrix(b.trace_commit, b.trace_opened, b.trace_witnesses, width);
-        if (has_perm_commit) matrix(lk.permutation_commit, lk.permutation_opened, lk.permutation_witnesses, perm_width);
-        for (uint32_t c = 0; c < num_chunks; c++)
-            claims.push_back({b.quotient_commit + c, b.quotient_opened + c, b.quotient_witnesses + c, 1, zeta});
-        if (pre_width > 0) matrix(in.vk_commitment, pp.preprocessed_opened, pp.preprocessed_witnesses, pre_width);
-        // what the reference's deserialisation would refuse is no opening (as in the per-column mode)
-        for (const Claim& c : claims) {
-            for (uint32_t j = 0; j < c.w; j++)
-                if (!fr_is_canonical(Fr::from_abi(c.values[j])))
-                    return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                                   "malformed opening: an opened value is not a canonical Fr");
-            for (uint32_t j = 0; j < c.w; j++)
-                if (!g1_valid(c.commit[j]))
-                    return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                                   "malformed opening: a commitment is not a point of G1");
-            if (!g1_valid(*c.witness))
-                return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                               "malformed opening: a witness is not a point of G1");
-        }
-        out.gamma = in.gamma;
-        out.delta = in.delta;
-        if (challenger) {
-            for (const Claim& c : claims)
-                for (uint32_t j = 0; j < c.w; j++) challenger->observe(Fr::from_abi(c.values[j]));
-            out.gamma = challenger->sample();
-            for (const Claim& c : claims) challenger->observe_g1(c.witness, 1);
-            out.delta = challenger->sample();
-        } else if (!fr_is_canonical(out.gamma) || !fr_is_canonical(out.delta)) {
-            throw Error(EON_E_ARG, "gamma or delta is not a canonical Fr");
-        }
-        // Every scaled point from ONE variable-base column MSM: the bases are the proof's commitments
-        // (a matrix's once, shared by its two claims) followed by the K witnesses; column i of the
-        // scalar matrix holds delta^i gamma^j on the rows of claim i's commitments and gives
-        // delta^i C_i, column K + i holds delta^i on the row of W_i and gives delta^i W_i.
-        const size_t K = claims.size();
-        std::vector<eon_g1_affine> pts;
-        std::vector<size_t> first(K);
-        for (size_t i = 0; i < K; i++) {
-            if (i > 0 && claims[i].commit == claims[i - 1].commit) {
-                first[i] = first[i - 1];
-                continue;
-            }
-            first[i] = pts.size();
-            pts.insert(pts.end(), claims[i].commit, claims[i].commit + claims[i].w);
-        }
-        const size_t wit0 = pts.size();
-        for (const Claim& c : claims) pts.push_back(*c.witness);
-        const size_t n_pts = pts.size(), cols = 2 * K;
-        std::vector<eon_fr> scal(n_pts * cols, eon_fr{{0, 0, 0, 0}});
-        std::vector<eon_fr> vs(K), zs(K);
-        Fr dpow = Fr::one();
-        for (size_t i = 0; i < K; i++) {
-            const Claim& c = claims[i];
-            Fr s = dpow, v = Fr::zero();
-            for (uint32_t j = 0; j < c.w; j++) {
-                scal[(first[i] + j) * cols + i] = s.abi();
-                v = fr_sum(v, fr_mul(s, Fr::from_abi(c.values[j])));
-                s = fr_mul(s, out.gamma);
-            }
-            scal[(wit0 + i) * cols + K + i] = dpow.abi();
-            vs[i] = v.abi();
-            zs[i] = c.z.abi();
-            dpow = fr_mul(dpow, out.delta);
-        }
-        std::vector<eon_g1_affine> scaled(cols);
-        {
-            eon_msm_bases* bases = nullptr;
-            check(ctx, eon_msm_bases_create(ctx, pts.data(), n_pts, 0, &bases), "eon_msm_bases_create");
-            const int mrc = eon_msm_g1_columns(ctx, bases, scal.data(), n_pts, (uint32_t)cols, scaled.data());
-            eon_msm_bases_destroy(bases);
-            check(ctx, mrc, "eon_msm_g1_columns");
-        }
-        int ok = 0;
-        const int rc = eon_kzg_verify_batch(ctx, scaled.data(), scaled.data() + K, vs.data(), zs.data(), K,
-                                            &pcs.g2_alpha(), &ok);
-        if (rc == EON_E_ARG) {
-            const char* msg = eon_last_error(ctx);
-            return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                           std::string("malformed opening: ") + (msg ? msg : "invalid argument"));
-        }
-        check(ctx, rc, "eon_kzg_verify_batch");
-        if (!ok)
-            return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                           "KzgError::ProofShapeMismatch: the weighted pairing check of " + std::to_string(K) +
-                               " batched openings failed");
+// ---- phase 2: the openings of every live proof, one segment each --------------------------------
+void check_openings(KzgPcs& pcs, const std::vector<Prepared*>& live) {
+    eon_ctx* ctx = pcs.ctx();
+    if (live.empty()) return;
+    for (Prepared* p : live)
+        if (p->batched) scale_claims(ctx, *p);
+    std::vector<int> status(live.size(), 0);
+    std::vector<std::string> why(live.size());
+    if (live.size() == 1) {
+        status[0] = openings_alone(pcs, *live[0], &why[0]);
     } else {
-        // the reference's round order: trace at {zeta, zeta h}, permutation at {zeta, zeta h}, quotient
-        // chunks at {zeta}, preprocessed at {zeta, zeta h} (:415-471)
         std::vector<eon_g1_affine> cs, ws;
         std::vector<eon_fr> vs, zs;
-        auto matrix = [&](const eon_g1_affine* commit, const eon_fr* opened, const eon_g1_affine* wit, uint32_t w) {
-            const Fr pts[2] = {zeta, zeta_next};
-            for (int p = 0; p < 2; p++)
-                for (uint32_t c = 0; c < w; c++) {
-                    cs.push_back(commit[c]);
-                    ws.push_back(wit[(size_t)p * w + c]);
-                    vs.push_back(opened[(size_t)p * w + c]);
-                    zs.push_back(pts[p].abi());
-                }
-        };
-        matrix(b.trace_commit, b.trace_opened, b.trace_witnesses, width);
-        if (has_perm_commit) matrix(lk.permutation_commit, lk.permutation_opened, lk.permutation_witnesses, perm_width);
-        for (uint32_t c = 0; c < num_chunks; c++) {
-            cs.push_back(b.quotient_commit[c]);
-            ws.push_back(b.quotient_witnesses[c]);
-            vs.push_back(b.quotient_opened[c]);
-            zs.push_back(zeta.abi());
+        std::vector<uint64_t> seg(1, 0);
+        for (const Prepared* p : live) {
+            cs.insert(cs.end(), p->cs.begin(), p->cs.end());
+            ws.insert(ws.end(), p->ws.begin(), p->ws.end());
+            vs.insert(vs.end(), p->vs.begin(), p->vs.end());
+            zs.insert(zs.end(), p->zs.begin(), p->zs.end());
+            seg.push_back(cs.size());
         }
-        if (pre_width > 0) matrix(in.vk_commitment, pp.preprocessed_opened, pp.preprocessed_witnesses, pre_width);
-        int ok = 0;
-        const int rc = eon_kzg_verify_batch(ctx, cs.data(), ws.data(), vs.data(), zs.data(), cs.size(),
-                                            &pcs.g2_alpha(), &ok);
-        // a commitment or witness that is no curve point, or an opened value that is no canonical
-        // Fr, cannot come out of the reference's deserialisation: not an opening
-        if (rc == EON_E_ARG) {
-            const char* msg = eon_last_error(ctx);
-            return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                           std::string("malformed opening: ") + (msg ? msg : "invalid argument"));
-        }
-        check(ctx, rc, "eon_kzg_verify_batch");
-        if (!ok)
-            return verdict(out, EON_VERIFY_INVALID_OPENING_ARGUMENT,
-                           "KzgError::ProofShapeMismatch: the batched pairing check of " + std::to_string(cs.size()) +
-                               " openings failed");
+        check(ctx,
+              eon_kzg_verify_batch_many(ctx, cs.data(), ws.data(), vs.data(), zs.data(), seg.data(),
+                                        (uint32_t)live.size(), &pcs.g2_alpha(), status.data()),
+              "eon_kzg_verify_batch_many");
+        // the message of a malformed segment is the single call's on that segment
+        for (size_t i = 0; i < live.size(); i++)
+            if (status[i] == EON_E_ARG && openings_alone(pcs, *live[i], &why[i]) != EON_E_ARG)
+                throw Error(EON_E_DEVICE, "eon_kzg_verify_batch_many and eon_kzg_verify_batch disagree on a segment");
     }
+    for (size_t i = 0; i < live.size(); i++) {
+        Prepared& p = *live[i];
+        if (status[i] == EON_E_ARG)
+            reject(p, EON_VERIFY_INVALID_OPENING_ARGUMENT, "malformed opening: " + why[i]);
+        else if (!status[i])
+            reject(p, EON_VERIFY_INVALID_OPENING_ARGUMENT,
+                   std::string("KzgError::ProofShapeMismatch: the ") + (p.batched ? "weighted" : "batched") +
+                       " pairing check of " + std::to_string(p.cs.size()) + (p.batched ? " batched" : "") +
+                       " openings failed");
+    }
+}
 
-    // ---- 4. quotient(zeta) (:476-480) -----------------------------------------------------------
-    std::vector<Fr> chunks(num_chunks);
-    for (uint32_t c = 0; c < num_chunks; c++) chunks[c] = Fr::from_abi(b.quotient_opened[c]);
-    const Fr quotient = recompose_quotient(log_n, log_qd, chunks.data(), zeta);
-
-    // ---- 5. verify_constraints (:77-160) --------------------------------------------------------
-    SelectorsAtPoint sels;
-    if (!selectors_at_point(log_n, zeta, &sels))  // the reference panics: inverse of zero
-        throw Error(EON_E_ARG, "zeta lies on the trace domain: the selectors at zeta are undefined");
+// ---- phase 3: constraints(zeta) / Z_H(zeta) against quotient(zeta) for the proofs that passed ---
+// `ins[p.index]` are the inputs proof p was prepared from; `many`: the messages name the index.
+void check_ood(KzgPcs& pcs, const ProgShape& ps, const VerifyInputs* ins, const std::vector<Prepared*>& live,
+               bool many) {
+    eon_ctx* ctx = pcs.ctx();
+    if (live.empty()) return;
+    for (const Prepared* p : live)
+        if (p->zeta_on_domain)
+            throw Error(EON_E_ARG, (many ? "proof " + std::to_string(p->index) + ": " : std::string()) +
+                                       "zeta lies on the trace domain: the selectors at zeta are undefined");
+    const uint32_t width = ps.width, perm_width = ps.perm_width, pre_width = live[0]->pre_width;
+    const size_t n = live.size(), stride = live[0]->rows.size();
+    const uint32_t n_ch = (uint32_t)live[0]->out.challenges.size();
+    std::vector<eon_fr> host(n * stride), ch(std::max<size_t>(n * n_ch, 1)), pub(std::max<size_t>(n * ps.n_public, 1));
+    std::vector<eon_fr> alpha(n), zeta(n), res(2 * n);
+    std::vector<uint32_t> log_n(n);
+    for (size_t i = 0; i < n; i++) {
+        const Prepared& p = *live[i];
+        std::memcpy(host.data() + i * stride, p.rows.data(), stride * sizeof(eon_fr));
+        for (uint32_t j = 0; j < n_ch; j++) ch[i * n_ch + j] = p.out.challenges[j].abi();
+        for (uint32_t j = 0; j < ps.n_public; j++) pub[i * ps.n_public + j] = ins[p.index].publics[j];
+        alpha[i] = p.out.alpha.abi();
+        zeta[i] = p.out.zeta.abi();
+        log_n[i] = p.log_n;
+    }
     // the opened rows on the device: local | next | pre_local | pre_next | perm_local | perm_next
-    const size_t total = 2 * ((size_t)width + pre_width + perm_width);
-    DeviceBuffer rows(std::max<size_t>(total, 1) * sizeof(eon_fr));
+    DeviceBuffer rows(host.size() * sizeof(eon_fr));
     hipStream_t stream = static_cast<hipStream_t>(eon_ctx_stream(ctx));
-    std::vector<eon_fr> host(std::max<size_t>(total, 1));
-    std::memcpy(host.data(), b.trace_opened, 2 * (size_t)width * sizeof(eon_fr));
-    if (pre_width) std::memcpy(host.data() + 2 * width, pp.preprocessed_opened, 2 * (size_t)pre_width * sizeof(eon_fr));
-    if (perm_width)
-        std::memcpy(host.data() + 2 * (width + pre_width), lk.permutation_opened,
-                    2 * (size_t)perm_width * sizeof(eon_fr));
     if (hipMemcpyAsync(rows.get(), host.data(), host.size() * sizeof(eon_fr), hipMemcpyHostToDevice, stream) !=
             hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess)
         throw Error(EON_E_DEVICE, "copying the opened values to the device failed");
     const eon_fr* d = rows.as<eon_fr>();
-    const eon_fr* d_pre = d + 2 * width;
-    const eon_fr* d_perm = d_pre + 2 * pre_width;
-    std::vector<eon_fr> ch(std::max<size_t>(out.challenges.size(), 1));
-    for (size_t i = 0; i < out.challenges.size(); i++) ch[i] = out.challenges[i].abi();
-    const eon_fr a = out.alpha.abi(), z = zeta.abi();
-    eon_fr res[2];
-    check(ctx,
-          eon_air_eval_at_point_dev(ctx, in.prog, log_n, &z, &a, d, d + width, pre_width ? d_pre : nullptr,
-                                    pre_width ? d_pre + pre_width : nullptr, perm_width ? d_perm : nullptr,
-                                    perm_width ? d_perm + perm_width : nullptr, in.publics, in.n_public, ch.data(),
-                                    (uint32_t)out.challenges.size(), res),
-          "eon_air_eval_at_point_dev");
-    if (!(Fr::from_abi(res[1]) == quotient))  // :155
-        return verdict(out, EON_VERIFY_OOD_EVALUATION_MISMATCH,
-                       "constraints(zeta) / Z_H(zeta) differs from quotient(zeta)");
+    if (n == 1) {
+        const eon_fr* d_pre = d + 2 * width;
+        const eon_fr* d_perm = d_pre + 2 * pre_width;
+        try {
+            check(ctx,
+                  eon_air_eval_at_point_dev(ctx, ins[live[0]->index].prog, log_n[0], &zeta[0], &alpha[0], d, d + width,
+                                            pre_width ? d_pre : nullptr, pre_width ? d_pre + pre_width : nullptr,
+                                            perm_width ? d_perm : nullptr, perm_width ? d_perm + perm_width : nullptr,
+                                            ins[live[0]->index].publics, ps.n_public, ch.data(), n_ch, res.data()),
+                  "eon_air_eval_at_point_dev");
+        } catch (const Error& e) {
+            if (!many) throw;
+            throw Error(e.code, "proof " + std::to_string(live[0]->index) + ": " + e.what());
+        }
+    } else {
+        const int rc = eon_air_eval_at_points_dev(ctx, ins[live[0]->index].prog, (uint32_t)n, log_n.data(),
+                                                  zeta.data(), alpha.data(), d, stride, pub.data(), ch.data(), n_ch,
+                                                  res.data());
+        if (rc != EON_OK) {
+            // the library names the point among those it was given: name the caller's proof instead
+            const char* raw = eon_last_error(ctx);
+            std::string msg = raw ? raw : "error";
+            size_t j = 0;
+            int used = 0;
+            if (sscanf(msg.c_str(), "point %zu:%n", &j, &used) == 1 && used > 0 && j < n)
+                msg = "proof " + std::to_string(live[j]->index) + ":" + msg.substr((size_t)used);
+            throw Error(rc, "eon_air_eval_at_points_dev: " + msg);
+        }
+    }
+    for (size_t i = 0; i < n; i++)
+        if (!(Fr::from_abi(res[2 * i + 1]) == live[i]->quotient))  // :155
+            reject(*live[i], EON_VERIFY_OOD_EVALUATION_MISMATCH,
+                   "constraints(zeta) / Z_H(zeta) differs from quotient(zeta)");
+}
+
+}  // namespace
+
+VerifyOutcome verify(KzgPcs& pcs, const VerifyInputs& in, DuplexChallenger* challenger) {
+    const ProgShape ps = prog_shape(pcs.ctx(), in.prog);
+    Prepared p = prepare(pcs.max_degree(), ps, in, challenger);
+    std::vector<Prepared*> live;
+    if (!p.done) live.push_back(&p);
+    check_openings(pcs, live);
+    if (p.done) live.clear();
+    check_ood(pcs, ps, &in, live, false);
+    return p.out;
+}
+
+std::vector<VerifyOutcome> verify_many(KzgPcs& pcs, const std::vector<VerifyInputs>& ins,
+                                       const std::vector<DuplexChallenger*>& challengers) {
+    const size_t n = ins.size();
+    if (n == 0) return {};
+    if (!challengers.empty() && challengers.size() != n) throw Error(EON_E_ARG, "one challenger per proof, or none");
+    for (size_t i = 0; i < n; i++)
+        if (ins[i].prog != ins[0].prog) throw Error(EON_E_ARG, "proof " + std::to_string(i) + ": another AIR program");
+    const ProgShape ps = prog_shape(pcs.ctx(), ins[0].prog);
+    // phase 1 on min(n, 8) threads (a constant, not the machine's CPU count): thread t prepares
+    // proofs t, t + T, ...; the proofs share nothing but read-only inputs
+    std::vector<Prepared> prepared(n);
+    std::vector<std::exception_ptr> failed(n);
+    const size_t T = std::min<size_t>(n, VERIFY_PREPARE_THREADS);
+    auto work = [&](size_t t) {
+        for (size_t i = t; i < n; i += T) {
+            try {
+                prepared[i] = prepare(pcs.max_degree(), ps, ins[i], challengers.empty() ? nullptr : challengers[i]);
+                prepared[i].index = i;
+            } catch (...) {
+                failed[i] = std::current_exception();
+            }
+        }
+    };
+    if (T == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (size_t t = 0; t < T; t++) pool.emplace_back(work, t);
+        for (std::thread& th : pool) th.join();
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (!failed[i]) continue;
+        try {
+            std::rethrow_exception(failed[i]);
+        } catch (const Error& e) {
+            throw Error(e.code, "proof " + std::to_string(i) + ": " + e.what());
+        }
+    }
+    std::vector<Prepared*> live;
+    for (Prepared& p : prepared)
+        if (!p.done) live.push_back(&p);
+    check_openings(pcs, live);
+    live.erase(std::remove_if(live.begin(), live.end(), [](const Prepared* p) { return p->done; }), live.end());
+    check_ood(pcs, ps, ins.data(), live, true);
+    std::vector<VerifyOutcome> out;
+    for (Prepared& p : prepared) out.push_back(std::move(p.out));
     return out;
 }
 
 }  // namespace eon_host
+

@@ -12,37 +12,29 @@
 #include "eon_prove.h"
 #include "pcs.h"
 #include "transcript.h"
+#include "verify_prepare.h"
 
 namespace eon_host {
-
-struct VerifyInputs {
-    const eon_air_program* prog = nullptr;
-    const eon_proof_lk* proof = nullptr;  // the superset of the proof structs; NULL arrays = absent
-    const eon_fr* publics = nullptr;
-    uint32_t n_public = 0;
-    // PreprocessedVerifierKey (preprocessed.rs:30-40) as plain values; vk_commitment NULL = no key
-    uint32_t vk_width = 0, vk_degree_bits = 0;
-    const eon_g1_affine* vk_commitment = nullptr;
-    // without a challenger: the challenges the proof was made with
-    const eon_fr* challenges = nullptr;
-    uint32_t n_challenges = 0;
-    Fr alpha = Fr::zero(), zeta = Fr::zero();
-    // EON_OPENING_BATCHED: the witness arrays of the proof hold ONE point per opened point ([2],
-    // [2], [C], [2]); without a challenger gamma and delta are the ones given here
-    bool batched = false;
-    Fr gamma = Fr::zero(), delta = Fr::zero();
-};
-
-struct VerifyOutcome {
-    int verdict = EON_VERIFY_OK;  // EON_VERIFY_*
-    std::string detail;           // why, when not OK
-    Fr alpha = Fr::zero(), zeta = Fr::zero();  // the challenges used (sampled with a challenger)
-    std::vector<Fr> challenges;
-    Fr gamma = Fr::zero(), delta = Fr::zero();  // batched mode: the opening challenges used
-};
 
 // Throws Error for bad arguments and device errors (negative codes); every other outcome is a
 // verdict.  `challenger` (nullable) is advanced exactly as the reference's verifier advances its own.
 VerifyOutcome verify(KzgPcs& pcs, const VerifyInputs& in, DuplexChallenger* challenger);
+
+// A batch of proofs of ONE program against one pcs, one outcome per proof: outcome i -- verdict,
+// detail, the challenges used -- and the end state of challengers[i] are exactly those of verify on
+// proof i alone.  verify's three phases, each over the whole batch:
+//   1. prepare, per proof and without a device: shapes, the transcript, the openings in the
+//      reference's round order, quotient(zeta); on min(n, VERIFY_PREPARE_THREADS) threads.  A proof
+//      rejected here has its verdict and leaves the batch;
+//   2. the openings of every remaining proof in ONE eon_kzg_verify_batch_many, a segment per proof
+//      (every proof keeps its own Gt product: no weights across proofs).  A batched-mode proof's
+//      gamma / delta scaling stays one column MSM per proof, run in sequence before it;
+//   3. ONE eon_air_eval_at_points_dev over the proofs whose openings passed -- a proof that fails
+//      its openings is never reported as an out-of-domain mismatch.
+// `challengers`: empty (the given challenges of every input), or one per proof.  What throws in
+// verify throws here with "proof i: " before the message, and no outcome is returned.
+constexpr size_t VERIFY_PREPARE_THREADS = 8;
+std::vector<VerifyOutcome> verify_many(KzgPcs& pcs, const std::vector<VerifyInputs>& ins,
+                                       const std::vector<DuplexChallenger*>& challengers);
 
 }  // namespace eon_host

@@ -125,6 +125,12 @@ SIGNATURES = {
                               ctypes.POINTER(_INT)]),
     "eon_verify_air_fs": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _P, _U32, _U32, _U32, _P, _P,
                                  ctypes.POINTER(_INT), _P, _P, _P]),
+    "eon_verify_air_many": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _U32, _P, _U32, _U32, _U32, _P, _P, _U32,
+                                   _P, _P, _P, _P, _P]),
+    "eon_verify_air_many_fs": (_INT, [_P, _P, ctypes.POINTER(eon_proof_lk), _U32, _P, _U32, _U32, _U32, _P, _P, _P,
+                                      _P, _P, _P]),
+    "eon_verify_many_detail": (ctypes.c_char_p, [_P, _U32]),
+    "eon_verify_many_opening_challenges": (_INT, [_P, _U32, _P, _P]),
 }
 
 _plib = None
@@ -511,26 +517,21 @@ def setup_preprocessed(pcs: NativeKzgPcs, pre_trace) -> Preprocessed:
     return Preprocessed(pcs, h)
 
 
-def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: Challenger | None = None,
-                  preprocessed_vk=None, transcript: dict | None = None) -> None:
-    """verify_with_preprocessed (eon-uni-stark/src/verifier.rs:244-502) through the C++ driver
-    (eon_verify_air[_fs]).  `prog` is the air.AirProgram of the AIR (for a Poseidon2 proof of the
-    fused kernel: AirProgram(Poseidon2Air), the same constraints in the same order); `proof` has
-    prove_native's shape; `preprocessed_vk` is the verifier key, a Preprocessed or a
-    (width, degree_bits, commitment) tuple -- its commitment is the one observed and checked, never
-    the proof's copy.  With `challenger` the challenges are re-derived from the transcript and the
-    challenger ends where the prover's did; without, proof.alpha, proof.zeta and
-    proof.permutation_challenges are used.  `transcript` (a dict, optional) receives the alpha, zeta
-    and permutation_challenges the verifier used.  Returns None when the proof is valid; raises
-    VerificationError whose `.kind` names the reference's variant.  Array shapes that do not fit the
-    program (opened widths, the chunk count, the permutation width, the key's width) raise
-    InvalidProofShape before any C call."""
-    if public_values is None:
-        public_values = ()
-    from .air import _publics_limbs
+class _Marshalled:
+    """A proof as the C ABI takes it: the eon_proof_lk, the arrays that back its pointers (kept alive
+    here), and what verify_native reads off the proof and the verifier key on the way."""
 
-    def bad_shape(why):
-        return VerificationError("InvalidProofShape", why)
+    __slots__ = ("lk", "keep", "opening", "batched", "has_perm", "vk_w", "vk_bits", "vk_c")
+
+
+def _bad_shape(why):
+    return VerificationError("InvalidProofShape", why)
+
+
+def _marshal_proof(prog, proof, preprocessed_vk) -> _Marshalled:
+    """verify_native's marshalling, shared with verify_native_many: array shapes that do not fit the
+    program raise InvalidProofShape here, before any C call."""
+    bad_shape = _bad_shape
 
     def mat(a, cols):
         return np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(-1, cols))
@@ -597,6 +598,34 @@ def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: 
     out_pp = eon_proof_pp(out, None, _p(po) if po is not None else None, _p(pw) if pw is not None else None)
     out_lk = eon_proof_lk(out_pp, _p(mc) if mc is not None else None, _p(mo) if mo is not None else None,
                           _p(mw) if mw is not None else None)
+    m = _Marshalled()
+    m.lk, m.keep = out_lk, (tc, qc, to, tw, qo, qw, po, pw, mc, mo, mw, vk_c)
+    m.opening, m.batched, m.has_perm = opening, batched, has_perm
+    m.vk_w, m.vk_bits, m.vk_c = vk_w, vk_bits, vk_c
+    return m
+
+
+def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: Challenger | None = None,
+                  preprocessed_vk=None, transcript: dict | None = None) -> None:
+    """verify_with_preprocessed (eon-uni-stark/src/verifier.rs:244-502) through the C++ driver
+    (eon_verify_air[_fs]).  `prog` is the air.AirProgram of the AIR (for a Poseidon2 proof of the
+    fused kernel: AirProgram(Poseidon2Air), the same constraints in the same order); `proof` has
+    prove_native's shape; `preprocessed_vk` is the verifier key, a Preprocessed or a
+    (width, degree_bits, commitment) tuple -- its commitment is the one observed and checked, never
+    the proof's copy.  With `challenger` the challenges are re-derived from the transcript and the
+    challenger ends where the prover's did; without, proof.alpha, proof.zeta and
+    proof.permutation_challenges are used.  `transcript` (a dict, optional) receives the alpha, zeta
+    and permutation_challenges the verifier used.  Returns None when the proof is valid; raises
+    VerificationError whose `.kind` names the reference's variant.  Array shapes that do not fit the
+    program (opened widths, the chunk count, the permutation width, the key's width) raise
+    InvalidProofShape before any C call."""
+    if public_values is None:
+        public_values = ()
+    from .air import _publics_limbs
+
+    m = _marshal_proof(prog, proof, preprocessed_vk)
+    out_lk, opening, batched, has_perm = m.lk, m.opening, m.batched, m.has_perm
+    vk_w, vk_bits, vk_c = m.vk_w, m.vk_bits, m.vk_c
     pub = _publics_limbs(public_values)
     npub = len(public_values)
     pcs.ctx.set_stream(None)
@@ -606,7 +635,7 @@ def verify_native(prog, pcs: NativeKzgPcs, proof, public_values=(), challenger: 
     if challenger is None:
         chal = [int(c) for c in (proof.permutation_challenges or ())] if has_perm else []
         if len(chal) != (prog.num_challenges if has_perm else 0):
-            raise bad_shape(f"{len(chal)} permutation challenges, the AIR has {prog.num_challenges}")
+            raise _bad_shape(f"{len(chal)} permutation challenges, the AIR has {prog.num_challenges}")
         ch = _publics_limbs(chal)
         a, z = fr_to_abi(proof.alpha), fr_to_abi(proof.zeta)
         with pcs.opening_scope(opening, proof.gamma if batched else None, proof.delta if batched else None):
@@ -771,6 +800,134 @@ def verify_native_bytes(prog, pcs: NativeKzgPcs, data, public_values=(), challen
         raise ValueError("proof bytes carry no challenges: verify them with a challenger")
     proof = proof_from_bytes(data, pcs.ctx)
     return verify_native(prog, pcs, proof, public_values, challenger, preprocessed_vk, transcript)
+
+
+def verify_native_many(prog, pcs: NativeKzgPcs, proofs, public_values=None, challengers=None, preprocessed_vk=None,
+                       transcripts=None) -> list:
+    """verify_native over a batch of proofs of one AIR in one pass (eon_verify_air_many[_fs]): the
+    host part of every proof on a few threads, every proof's openings as one segment of ONE
+    segmented pairing check, ONE launch for the constraints at every zeta.  Entry i of the result is
+    None for a valid proof, else the VerificationError verify_native would have raised for proof i
+    alone -- the InvalidProofShape it raises before any C call included.  `public_values`: one
+    sequence per proof (None: no public values); `challengers`: one Challenger per proof, each left
+    where verify_native leaves it, or None for the challenges the proofs carry; `transcripts`: a list
+    of dicts, entry i updated as verify_native's `transcript`.  `preprocessed_vk`: the verifier key
+    of every proof, or a list with one key per proof.  Proofs are grouped by opening mode (and by
+    key, when several are given), one C call per group.  What verify_native raises as an EonError (a
+    zeta on the trace domain, a wrong public value count) is raised here for the whole batch, its
+    message naming the proof's index in `proofs`.  An entry of `proofs` that is already an
+    exception is passed through (verify_native_bytes_many)."""
+    from .air import _publics_limbs
+
+    n = len(proofs)
+    if n == 0:
+        return []
+    publics = [()] * n if public_values is None else [() if p is None else p for p in public_values]
+    if len(publics) != n or (challengers is not None and len(challengers) != n) or \
+            (transcripts is not None and len(transcripts) != n):
+        raise ValueError("one sequence of public values, one challenger and one transcript per proof")
+    vks = list(preprocessed_vk) if isinstance(preprocessed_vk, list) else [preprocessed_vk] * n
+    if len(vks) != n:
+        raise ValueError("one verifier key per proof, or one for all")
+    results: list = [None] * n
+    live = {}
+    chals = {}
+    for i, proof in enumerate(proofs):
+        if isinstance(proof, Exception):
+            results[i] = proof
+            continue
+        try:
+            m = _marshal_proof(prog, proof, vks[i])
+            if challengers is None:
+                chal = [int(c) for c in (proof.permutation_challenges or ())] if m.has_perm else []
+                if len(chal) != (prog.num_challenges if m.has_perm else 0):
+                    raise _bad_shape(f"{len(chal)} permutation challenges, the AIR has {prog.num_challenges}")
+                chals[i] = chal
+            live[i] = m
+        except VerificationError as e:
+            results[i] = e
+    unm = lambda v: fr_unmont(sum(int(x) << (64 * i) for i, x in enumerate(v)))  # noqa: E731
+    n_ch = prog.num_challenges
+    pcs.ctx.set_stream(None)
+    def checked(rc, idx):
+        """pcs.check, with the "proof j:" of a C call's error turned into the caller's index"""
+        try:
+            pcs.check(rc)
+        except _lib.EonError as e:
+            import re
+
+            msg = pcs.lib.eon_kzg_pcs_last_error(pcs._h).decode()
+            raise _lib.EonError(e.code, re.sub(r"proof (\d+):", lambda g: f"proof {idx[int(g.group(1))]}:", msg,
+                                               count=1)) from None
+
+    groups = {}  # (opening mode, verifier key) -> the proofs of one C call, in order
+    for i in live:
+        groups.setdefault((live[i].opening, id(vks[i])), []).append(i)
+    for (opening, _), idx in groups.items():
+        k = len(idx)
+        batched = opening == "batched"
+        npub = len(publics[idx[0]])
+        if any(len(publics[i]) != npub for i in idx):
+            raise ValueError("every proof of a batch has the AIR's number of public values")
+        lks = (eon_proof_lk * k)(*[live[i].lk for i in idx])
+        pub = _publics_limbs([v for i in idx for v in publics[i]])
+        first = live[idx[0]]
+        vkp = _p(first.vk_c) if first.vk_c is not None else None
+        res = np.full(k, -1, dtype=np.int32)
+        if challengers is None:
+            ch = _publics_limbs([v for i in idx for v in (chals[i] + [0] * (n_ch - len(chals[i])))])
+            a = _publics_limbs([proofs[i].alpha for i in idx])
+            z = _publics_limbs([proofs[i].zeta for i in idx])
+            g = _publics_limbs([proofs[i].gamma for i in idx]) if batched else None
+            d = _publics_limbs([proofs[i].delta for i in idx]) if batched else None
+            with pcs.opening_scope(opening):
+                checked(pcs.lib.eon_verify_air_many(pcs._h, prog.handle, lks, k, _p(pub), npub, first.vk_w,
+                                                      first.vk_bits, vkp, _p(ch), n_ch, _p(a), _p(z),
+                                                      _p(g) if batched else None, _p(d) if batched else None,
+                                                      _p(res)), idx)
+            used = [{"alpha": proofs[i].alpha, "zeta": proofs[i].zeta, "permutation_challenges": chals[i]}
+                    for i in idx]
+        else:
+            handles = (ctypes.c_void_p * k)(*[challengers[i].handle for i in idx])
+            a_out, z_out = np.zeros((k, 4), np.uint64), np.zeros((k, 4), np.uint64)
+            c_out = np.zeros((k, max(1, n_ch), 4), np.uint64)
+            with pcs.opening_scope(opening):
+                checked(pcs.lib.eon_verify_air_many_fs(pcs._h, prog.handle, lks, k, _p(pub), npub, first.vk_w,
+                                                         first.vk_bits, vkp, handles, _p(res),
+                                                         _p(c_out.reshape(-1, 4)) if n_ch else None, _p(a_out),
+                                                         _p(z_out)), idx)
+            used = [{"alpha": unm(a_out[j]), "zeta": unm(z_out[j]),
+                     "permutation_challenges": [unm(c) for c in c_out[j][:n_ch]] if live[i].has_perm else []}
+                    for j, i in enumerate(idx)]
+        for j, i in enumerate(idx):
+            r = int(res[j])
+            if batched and r != 1:
+                g1, d1 = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+                _check(pcs.lib.eon_verify_many_opening_challenges(pcs._h, j, _p(g1), _p(d1)),
+                       "eon_verify_many_opening_challenges")
+                used[j]["gamma"], used[j]["delta"] = unm(g1), unm(d1)
+            if transcripts is not None and r != 1:  # a shape rejection comes before the transcript
+                transcripts[i].update(used[j])
+            if r != 0:
+                results[i] = VerificationError(VerificationError.KINDS[r],
+                                               pcs.lib.eon_verify_many_detail(pcs._h, j).decode())
+    return results
+
+
+def verify_native_bytes_many(prog, pcs: NativeKzgPcs, blobs, public_values=None, challengers=None,
+                             preprocessed_vk=None, transcripts=None) -> list:
+    """verify_native_many on proofs that arrived as bytes: entry i is a ProofFormatError when blob i
+    does not deserialise (that proof's challenger is left untouched), else as verify_native_many.
+    The bytes carry no challenge, so the challengers are required."""
+    if challengers is None:
+        raise ValueError("proof bytes carry no challenges: verify them with challengers")
+    proofs = []
+    for data in blobs:
+        try:
+            proofs.append(proof_from_bytes(data, pcs.ctx))
+        except ProofFormatError as e:
+            proofs.append(e)
+    return verify_native_many(prog, pcs, proofs, public_values, challengers, preprocessed_vk, transcripts)
 
 
 def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | None,
