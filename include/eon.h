@@ -257,6 +257,10 @@ int eon_diag_msm_g1_prepare_active_dev(eon_ctx* ctx, const eon_msm_bases* bases,
                                        eon_g1_affine* out, eon_msm_scalars** prepared);
 
 /* ABI version; bumped on any signature or struct-layout change.
+ *   16 also carries, added later without a bump (new symbols only, no signature or layout of
+ *       version 16 changed; a binding that needs them looks the symbols up): the column-sharded
+ *       prove's device side -- eon_shard_column_range / _row_range, eon_shard_pack_rows_dev /
+ *       _unpack_cols_dev and eon_quotient_values_rows_dev;
  *   16: many checks in one pass -- eon_multi_pairing_many, eon_kzg_verify_batch_many and
  *       eon_air_eval_at_points_dev, additive;
  *   15: eon_diag_msm_scalars_order, a column batch's bucket order and piece-sum route, additive;
@@ -627,6 +631,16 @@ int eon_quotient_values_lk_dev(eon_ctx* ctx, const eon_air_program* prog, const 
                                const eon_fr* pre_lde, const eon_fr* perm_lde, uint32_t log_n, uint32_t log_qd,
                                const eon_fr* alpha, const eon_fr* publics, uint32_t n_public,
                                const eon_fr* challenges, uint32_t n_challenges, eon_fr* out);
+/* eon_quotient_values_dev on a block of rows, from a WINDOW of the LDE (the column-sharded prove,
+ * below): `window` = the n_rows + 2^log_qd LDE rows (row0 + j) mod Q, j < n_rows + 2^log_qd,
+ * Q = 2^(log_n + log_qd), row-major, width columns, device.  out[t] (device, n_rows Fr), t < n_rows,
+ * is eon_quotient_values_dev's out[row0 + t] bit for bit: local = window row t, next = window row
+ * t + 2^log_qd, the selectors and inv_vanishing of row row0 + t.  row0 + n_rows <= Q (EON_E_SHAPE
+ * otherwise); n_rows = 0 does nothing.  A program with preprocessed or permutation columns is
+ * EON_E_ARG. */
+int eon_quotient_values_rows_dev(eon_ctx* ctx, const eon_air_program* prog, const eon_fr* window, uint32_t log_n,
+                                 uint32_t log_qd, uint64_t row0, uint64_t n_rows, const eon_fr* alpha,
+                                 const eon_fr* publics, uint32_t n_public, eon_fr* out);
 /* LogUpGadget::generate_permutation (logup.rs:379-562) for a program with a lookup description:
  * `trace` = the main trace (device, height x width, height a power of two), `pre_trace` = the
  * preprocessed trace on the same (trace) domain, publics / challenges host arrays, perm_out =
@@ -774,6 +788,29 @@ int eon_fourstep_dft_dev(eon_ctx* ctx, const eon_fr* in, eon_fr* out, uint32_t l
  * bound collective, or one rank. */
 int eon_msm_sharded_dev(eon_ctx* ctx, const eon_msm_bases* bases, const eon_fr* scalars, uint64_t n_local,
                         const eon_collective* coll, eon_g1_affine* out);
+
+/* ---- column-sharded prove of a generic AIR (eon_prove_air_sharded, eon_prove.h) ----------------
+ * The partition.  Columns: rank g of `world` owns the contiguous range [c0, c0 + wl) of the `width`
+ * columns, in rank order, the first width % world ranks one column wider (wmax = ceil(width /
+ * world)).  Rows: with q_rows = Q quotient-domain rows and R = ceil(Q / world), rank r evaluates rows
+ * [row0, row0 + n_rows) = [min(Q, r R), min(Q, (r+1) R)), possibly none.  Its window is the R + S
+ * rows (r R + j) mod Q, j < R + S, where S = next_step = 2^log_qd.  Both are host-only and need no
+ * device; world = 0, rank >= world, and for the columns world > width, are EON_E_ARG. */
+int eon_shard_column_range(uint32_t width, uint32_t world, uint32_t rank, uint32_t* c0, uint32_t* wl);
+int eon_shard_row_range(uint64_t q_rows, uint32_t world, uint32_t rank, uint64_t* row0, uint64_t* n_rows);
+/* The two copies around the exchange (device pointers, on the context's stream).
+ *   pack:   lde = rank's q_rows x wl row-major LDE of its own columns; send receives `world` blocks
+ *           of (R + S) x wmax elements: block h, row j = LDE row (h R + j) mod Q, columns past wl zero.
+ *   (the caller's all_to_all, blocks of (R + S) wmax 32 bytes: recv block g = rank g's send block for
+ *   this rank)
+ *   unpack: recv = those `world` blocks; window receives the (R + S) x width row-major matrix of
+ *           window rows, columns [c0(g), c0(g) + wl(g)) from block g.
+ * q_rows and next_step powers of two, next_step <= q_rows <= 2^28 (EON_E_SHAPE); world > width is
+ * EON_E_ARG. */
+int eon_shard_pack_rows_dev(eon_ctx* ctx, const eon_fr* lde, uint64_t q_rows, uint32_t width, uint32_t world,
+                            uint32_t rank, uint64_t next_step, eon_fr* send);
+int eon_shard_unpack_cols_dev(eon_ctx* ctx, const eon_fr* recv, uint64_t q_rows, uint32_t width, uint32_t world,
+                              uint64_t next_step, eon_fr* window);
 
 /* ---- test SRS (setup, not prove time) --------------------------------------------------------
  * init_srs_unsafe's g1_powers (kzg/src/params.rs:123-139): out[i] = alpha^i * G1::generator(),

@@ -163,7 +163,8 @@ enum {
     EON_STAGE_COMMIT_TRACE = 0,    /* "commit to trace data" (prover.rs:186-187) */
     EON_STAGE_TRACE_LDE = 1,       /* get_evaluations_on_domain (prover.rs:315) */
     EON_STAGE_QUOTIENT = 2,        /* quotient_values (prover.rs:328-342) */
-    EON_STAGE_EXCHANGE = 3,        /* sharded: all-gather + combine of partial quotients */
+    EON_STAGE_EXCHANGE = 3,        /* sharded: all-gather + combine of partial quotients (lanes); the
+                                      window all_to_all + the quotient blocks' all-gather (columns) */
     EON_STAGE_COMMIT_QUOTIENT = 4, /* "commit to quotient poly chunks" (prover.rs:371-372) */
     EON_STAGE_OPEN = 5,            /* "open" (prover.rs:424-442) */
     EON_STAGE_ASSEMBLE = 6,        /* sharded: all-gather of per-column results */
@@ -237,6 +238,27 @@ int eon_prove_air(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* t
 int eon_prove_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
                      const eon_fr* publics, uint32_t n_public, eon_challenger* challenger, eon_proof* out,
                      eon_fr* alpha_out, eon_fr* zeta_out);
+
+/* Column-sharded prove of a program over a process group: eon_prove_air[_fs] with
+ * `shard` (world > 1; NULL or world <= 1 is eon_prove_air[_fs] itself).  Rank g owns the columns
+ * [c0, c0 + wl) of eon_shard_column_range(width(prog), world, g) (eon.h): `trace` is ITS height x wl
+ * slice on device, and it commits, extends and opens only those.  The trace commitments are
+ * all-gathered so every rank observes the full transcript; the ranks exchange their extended columns
+ * once as row blocks (eon_shard_pack_rows_dev, all_to_all, eon_shard_unpack_cols_dev), each
+ * evaluates the quotient on its own rows (eon_quotient_values_rows_dev) and the blocks are
+ * all-gathered; chunk c is then committed and opened by rank c % world, the opening bases are
+ * sharded over the group, and the per-column records are all-gathered.  Every rank's `out` (arrays
+ * of the FULL width W) is byte for byte the unsharded eon_prove_air[_fs] proof of the full trace.
+ * The collective needs all_gather and all_to_all.  EON_E_ARG, decided alike on every rank before
+ * the first collective call: world > W; a program with preprocessed columns or lookups; the
+ * check_constraints switch; the batched opening mode.  stage_ms[EON_STAGE_EXCHANGE] holds both data
+ * exchanges (the window and the quotient blocks). */
+int eon_prove_air_sharded(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                          const eon_fr* publics, uint32_t n_public, const eon_fr* alpha, const eon_fr* zeta,
+                          const eon_collective* shard, eon_proof* out);
+int eon_prove_air_sharded_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                             const eon_fr* publics, uint32_t n_public, eon_challenger* challenger,
+                             const eon_collective* shard, eon_proof* out, eon_fr* alpha_out, eon_fr* zeta_out);
 
 /* ---- preprocessed columns (eon-uni-stark/src/preprocessed.rs) -------------------------------
  * eon_preprocessed is PreprocessedProverData (preprocessed.rs:12-24): the width, degree_bits, the
@@ -515,7 +537,8 @@ int eon_verify_air_many_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const 
 const char* eon_verify_many_detail(const eon_kzg_pcs* pcs, uint32_t i);
 int eon_verify_many_opening_challenges(const eon_kzg_pcs* pcs, uint32_t i, eon_fr* gamma, eon_fr* delta);
 
-/* 11: eon_verify_air_many[_fs], eon_verify_many_detail / _opening_challenges, additive.
+/* 11 also carries eon_prove_air_sharded[_fs], added later without a bump (new symbols only).
+ * 11: eon_verify_air_many[_fs], eon_verify_many_detail / _opening_challenges, additive.
  * bumped on any signature or struct-layout change (4: the preprocessed surface above; 5: the lookup
  * surface above; 6: the check_constraints switch and report; 7: eon_verify_air[_fs]; 8:
  * eon_kzg_pcs_create_from_srs[_bytes] and eon_kzg_pcs_create_verifier; 9: the opening mode,

@@ -143,6 +143,10 @@ SIGNATURES = {
     "eon_ctx_set_serial": (_INT, [_P, _INT]),
     "eon_fourstep_dft_dev": (_INT, [_P, _P, _P, _U32, _INT, _P]),
     "eon_msm_sharded_dev": (_INT, [_P, _P, _P, _U64, _P, _P]),
+    "eon_shard_column_range": (_INT, [_U32, _U32, _U32, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    "eon_shard_row_range": (_INT, [_U64, _U32, _U32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "eon_shard_pack_rows_dev": (_INT, [_P, _P, _U64, _U32, _U32, _U32, _U64, _P]),
+    "eon_shard_unpack_cols_dev": (_INT, [_P, _P, _U64, _U32, _U32, _U64, _P]),
     "eon_ctx_serial": (_INT, [_P]),
     "eon_dft_batch": (_INT, [_P, _P, _P, _U64, _U32, _INT]),
     "eon_idft_batch": (_INT, [_P, _P, _P, _U64, _U32]),
@@ -218,6 +222,7 @@ SIGNATURES = {
     "eon_quotient_values_dev": (_INT, [_P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     "eon_quotient_values_pp_dev": (_INT, [_P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P]),
     "eon_quotient_values_lk_dev": (_INT, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _U32, _P, _U32, _P]),
+    "eon_quotient_values_rows_dev": (_INT, [_P, _P, _P, _U32, _U32, _U64, _U64, _P, _P, _U32, _P]),
     "eon_lookup_permutation_dev": (_INT, [_P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P]),
     "eon_check_constraints_dev": (_INT, [_P, _P, _P, _P, _P, _U64, _P, _U32, _P, _U32, _P, _P]),
     "eon_air_eval_at_point_dev": (_INT, [_P, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U32, _P, _U32, _P]),

@@ -419,6 +419,30 @@ class AirProgram:
             pub.ctypes.data_as(ctypes.c_void_p), len(publics), _dp(out)))
         return out
 
+    def quotient_values_rows(self, window, log_n: int, row0: int, n_rows: int, alpha, public_values=()):
+        """quotient_values on quotient-domain rows [row0, row0 + n_rows) alone, from a window of
+        the LDE (eon_quotient_values_rows_dev): `window` holds the n_rows + 2^log_qd LDE rows
+        (row0 + j) mod Q, j < n_rows + 2^log_qd, as (n_rows + 2^log_qd, width, 4).  Returns
+        (n_rows, 4): rows row0.. of quotient_values' output, bit for bit.  What a rank of the
+        column-sharded prove runs on its own rows (distributed.shard_row_range)."""
+        import torch
+
+        from .field import fr_to_abi
+
+        log_qd = self.log_quotient_degree()
+        rows = n_rows + (1 << log_qd)
+        w = window.contiguous()
+        if tuple(w.shape) != (rows, self.width, 4):
+            raise ValueError(f"window must be ({rows}, {self.width}, 4): n_rows + 2^log_qd rows of the AIR's width")
+        out = torch.empty((n_rows, 4), dtype=torch.int64, device=w.device)
+        a = fr_to_abi(alpha)
+        pub = _publics_limbs(public_values)
+        self.ctx.set_stream(torch.cuda.current_stream(w.device).cuda_stream)
+        self.ctx.check(self.ctx.lib.eon_quotient_values_rows_dev(
+            self.ctx.handle, self._h, _dp(w), log_n, log_qd, row0, n_rows, ctypes.byref(a),
+            pub.ctypes.data_as(ctypes.c_void_p), len(public_values), _dp(out)))
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self.ctx.lib.eon_air_program_destroy(self._h)

@@ -27,10 +27,13 @@
 // live in VGPRs, the rest in LDS (three planes: two 16-byte, one 4-byte; conflict-free accesses)
 // sized by the program's register count, or in a global buffer for very large programs.
 //
-// Structure: ONE interpreter (fetch, exec1, run_program over a Window and a MemRegs file) and FOUR
+// Structure: ONE interpreter (fetch, exec1, run_program over a Window and a MemRegs file) and FIVE
 // drivers, kernels that differ only in the rows they hand it and in what an ASSERT does (the
 // Window's Sink):
 //   k_air_quotient  quotient domain, next = row (i + 2^qd) mod Q, coset selectors, ASSERTs folded;
+//   k_air_quotient_rows  the same on n_rows quotient rows from row0, read from a WINDOW matrix
+//                   that holds rows row0 .. row0 + n_rows + 2^qd (mod Q) of the LDE (the
+//                   column-sharded prove, shard_exchange.hip): next = window row t + 2^qd, no wrap;
 //   k_lookup_terms  trace domain, next = row (i + 1) mod height, no selectors, no permutation
 //                   matrix; ASSERT k emits the lookups' k-th denominator or multiplicity;
 //   k_air_check     trace domain, all three matrices, 0 / 1 selectors synthesised from the row; every
@@ -437,6 +440,40 @@ __global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient(const CodeBlock* __r
     // = x y 2^256 (prover.rs:699)
     const F29 r = mul29<FrP>(acc, unpack29(ld_pinned(inv_van + (row & nr_mask))));
     st_vec(out + row, pack29<FrP>(canon29<FrP>(r)));
+}
+
+// The quotient on a block of rows (the column-sharded prove: every rank evaluates its own rows of
+// the quotient domain after the ranks exchanged their columns as row blocks).  `window` holds the
+// n_rows + next_step LDE rows (row0 + j) mod q, j < n_rows + next_step, row-major: thread t runs
+// the program with local = window row t and next = window row t + next_step (the wrap is in how the
+// window was gathered), and everything indexed by the position in the domain -- the coset
+// selectors, inv_vanishing -- is taken at the global row row0 + t.  out[t] is k_air_quotient's
+// out[row0 + t], bit for bit.  Main trace only (no PRE / PERM instance).  The global register file
+// is indexed by t over the n_rows of the launch.
+template <int MODE>
+__global__ void __launch_bounds__(AIR_BLOCK) k_air_quotient_rows(const CodeBlock* __restrict__ code, uint32_t n_blocks,
+                                                           uint32_t n_regs, const Fr* __restrict__ window,
+                                                           uint32_t width, uint64_t q, uint64_t next_step,
+                                                           uint64_t row0, uint64_t n_rows,
+                                                           const F29* __restrict__ table,
+                                                           const Fr* __restrict__ sels,
+                                                           const Fr* __restrict__ inv_van, uint32_t nr_mask, Fr alpha,
+                                                           Fr* __restrict__ out, uint4* __restrict__ gregs) {
+    extern __shared__ uint4 lds_regs[];
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_rows) return;
+    const uint64_t row = row0 + t;  // < q: the host checks row0 + n_rows <= q
+    auto w = make_window<false, false>(window, window, nullptr, nullptr, nullptr, nullptr, width, 0, 0, t,
+                                       t + next_step, q, table, sels);
+    w.row = row;  // the selectors' index
+    F29 acc;
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc.l[i] = 0;
+    MemRegs rf =
+        reg_file<MODE>(n_regs, lds_regs, gregs, MODE == 0 ? threadIdx.x : t, MODE == 0 ? blockDim.x : n_rows);
+    run_program(code, n_blocks, rf, w, uniform29(shl5_to261<FrP>(alpha)), acc);
+    const F29 r = mul29<FrP>(acc, unpack29(ld_pinned(inv_van + (row & nr_mask))));
+    st_vec(out + t, pack29<FrP>(canon29<FrP>(r)));
 }
 
 // ---- LogUp permutation trace: per-row contributions (generate_permutation, lookup/src/logup.rs:379-562)
@@ -1387,6 +1424,51 @@ int eon_quotient_values_dev(eon_ctx* ctx, const eon_air_program* prog, const eon
                                                   "eon_quotient_values_pp_dev with their LDE"));
     }
     return eon_quotient_values_pp_dev(ctx, prog, lde, nullptr, log_n, log_qd, alpha, publics, n_public, out);
+}
+
+int eon_quotient_values_rows_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* window, uint32_t log_n,
+                                 uint32_t log_qd, uint64_t row0, uint64_t n_rows, const eon_fr* alpha,
+                                 const eon_fr* publics, uint32_t n_public, eon_fr* out) {
+    if (!ctx || !prog_c) return EON_E_ARG;
+    auto* prog = const_cast<eon_air_program*>(prog_c);  // device scratch only
+    return with_ctx(ctx, [&]() -> Status {
+        if (prog->pre_width > 0 || prog->perm_width > 0 || prog->n_challenges > 0)
+            return Status::err(EON_E_ARG, "the windowed quotient takes a main trace only: the program reads "
+                                          "preprocessed or permutation columns");
+        EON_TRY(check_args(ctx, prog, !alpha || (n_rows && (!window || !out)), MatArg::none(), MatArg::none(), publics,
+                           n_public, nullptr, 0));
+        const uint32_t log_q = log_n + log_qd;
+        EON_TRY(check_domains(log_n, log_q));
+        const uint64_t q = 1ull << log_q;
+        if (row0 > q || n_rows > q - row0) return Status::err(EON_E_SHAPE, "row0 + n_rows exceeds the quotient domain");
+        const Fr al = fr_from_abi(alpha);
+        if (!fr_is_canonical(al)) return Status::err(EON_E_ARG, "alpha is not a canonical Fr");
+        if (n_rows == 0) return Status::ok();
+        EON_TRY(stage_table(ctx, prog, publics, n_public, nullptr, 0));
+        // the selector and vanishing tables of the whole domain, as eon_quotient_values_lk_dev makes
+        // them: the rows of this launch index into them at row0 + t
+        const Fr g5 = from_u64<FrP>(5);
+        const Fr* inv_van;
+        if (prog->uses_sels) {
+            EON_HIP(prog->d_sels.ensure(4 * q * sizeof(Fr)));
+            EON_TRY(selectors_launch(ctx, log_n, log_q, g5, prog->d_sels.as<Fr>()));
+            inv_van = prog->d_sels.as<Fr>() + 3 * q;
+        } else {
+            Fr *zh, *zh_inv;
+            EON_TRY(vanishing_table(ctx, log_n, log_q, g5, &zh, &zh_inv));
+            inv_van = zh_inv;
+        }
+        const uint32_t nr_mask = prog->uses_sels ? (uint32_t)(q - 1) : (1u << log_qd) - 1;
+        RegFile regs;
+        EON_TRY(plan_regs(prog, n_rows, &regs));
+        const Profile prof{"k_air_quotient_rows", (n_rows + (1ull << log_qd)) * prog->width * 32 + n_rows * 32,
+                           n_rows * (products(prog->code, true) + 1)};
+        return launch_air(
+            ctx, prog, regs, n_rows, code_blocks(prog->code.size()), prof, false, false,
+            [](auto m, auto, auto) { return k_air_quotient_rows<m()>; }, reinterpret_cast<const Fr*>(window),
+            prog->width, q, 1ull << log_qd, row0, n_rows, prog->d_table.as<F29>(),
+            prog->uses_sels ? prog->d_sels.as<Fr>() : nullptr, inv_van, nr_mask, al, reinterpret_cast<Fr*>(out));
+    });
 }
 
 int eon_lookup_permutation_dev(eon_ctx* ctx, const eon_air_program* prog_c, const eon_fr* trace,

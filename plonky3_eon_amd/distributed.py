@@ -75,6 +75,70 @@ def lane_range(rank: int, world: int, vector_len: int):
     return rank * per, (rank + 1) * per
 
 
+def column_range(width: int, world: int, rank: int):
+    """(c0, wl): the contiguous column range [c0, c0 + wl) of `rank` in the column-sharded prove of
+    a `width`-column AIR -- eon_shard_column_range's twin.  Rank order is column order, the first
+    width % world ranks own one column more; more ranks than columns is refused."""
+    if world < 1 or not 0 <= rank < world:
+        raise _lib.EonError(_lib.EON_E_ARG, f"rank {rank} outside world {world}")
+    if world > width:
+        raise _lib.EonError(_lib.EON_E_ARG, f"column sharding: more ranks than columns ({world} ranks, {width} columns)")
+    base, extra = divmod(width, world)
+    return rank * base + min(rank, extra), base + (1 if rank < extra else 0)
+
+
+def shard_row_range(q_rows: int, world: int, rank: int):
+    """(row0, n_rows): the quotient-domain rows rank `rank` evaluates, blocks of R = ceil(Q / world)
+    rows in rank order, the last ones short or empty -- eon_shard_row_range's twin."""
+    if world < 1 or not 0 <= rank < world or q_rows < 1:
+        raise _lib.EonError(_lib.EON_E_ARG, f"rank {rank} outside world {world}")
+    r = -(-q_rows // world)
+    lo, hi = min(q_rows, rank * r), min(q_rows, (rank + 1) * r)
+    return lo, hi - lo
+
+
+def window_rows(q_rows: int, world: int, rank: int, next_step: int):
+    """The LDE rows of rank `rank`'s window, in window order: (rank R + j) mod Q for j < R + S.
+    Window row t is the local row of the rank's t-th quotient row, window row t + S its next row."""
+    r = -(-q_rows // world)
+    return [(rank * r + j) % q_rows for j in range(r + next_step)]
+
+
+def shard_pack_rows(ctx, lde, width: int, world: int, rank: int, next_step: int):
+    """eon_shard_pack_rows_dev: the rank's (Q, wl, 4) LDE of its own columns -> the all_to_all's
+    send buffer (world, R + S, wmax, 4): block h = the rows of rank h's window, columns past wl zero."""
+    import torch
+
+    q = int(lde.shape[0])
+    _, wl = column_range(width, world, rank)
+    if tuple(lde.shape) != (q, wl, 4):
+        raise _lib.EonError(_lib.EON_E_SHAPE, f"rank {rank}'s LDE must be (Q, {wl}, 4)")
+    lde = lde.contiguous()
+    win, wmax = -(-q // world) + next_step, -(-width // world)
+    send = torch.empty((world, win, wmax, 4), dtype=torch.int64, device=lde.device)
+    ctx.set_stream(torch.cuda.current_stream(lde.device).cuda_stream)
+    ctx.check(ctx.lib.eon_shard_pack_rows_dev(ctx.handle, ctypes.c_void_p(lde.data_ptr()), q, width, world, rank,
+                                              next_step, ctypes.c_void_p(send.data_ptr())))
+    return send
+
+
+def shard_unpack_cols(ctx, recv, q_rows: int, width: int, next_step: int):
+    """eon_shard_unpack_cols_dev: the received blocks (world, R + S, wmax, 4), block g from rank g,
+    -> this rank's (R + S, width, 4) window, columns column_range(width, world, g) from block g."""
+    import torch
+
+    world = int(recv.shape[0])
+    win, wmax = -(-q_rows // world) + next_step, -(-width // world)
+    if tuple(recv.shape) != (world, win, wmax, 4):
+        raise _lib.EonError(_lib.EON_E_SHAPE, f"the received blocks must be ({world}, {win}, {wmax}, 4)")
+    recv = recv.contiguous()
+    window = torch.empty((win, width, 4), dtype=torch.int64, device=recv.device)
+    ctx.set_stream(torch.cuda.current_stream(recv.device).cuda_stream)
+    ctx.check(ctx.lib.eon_shard_unpack_cols_dev(ctx.handle, ctypes.c_void_p(recv.data_ptr()), q_rows, width, world,
+                                                next_step, ctypes.c_void_p(window.data_ptr())))
+    return window
+
+
 def lane_weights(alpha: int, vector_len: int, world: int, constraints_per_lane: int):
     """alpha^(K_lane (VL - l1_g)) for every rank g: the factor turning rank g's local folder
     accumulator into its share of the full one."""

@@ -335,6 +335,47 @@ int eon_prove_air_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr
     });
 }
 
+int eon_prove_air_sharded(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                          const eon_fr* publics, uint32_t n_public, const eon_fr* alpha, const eon_fr* zeta,
+                          const eon_collective* shard, eon_proof* out) {
+    if (!pcs || !pcs->pcs || !prog || !trace || !alpha || !zeta || !out || (n_public && !publics))
+        return EON_E_ARG;
+    if (!proof_arrays_ok(out)) return EON_E_ARG;
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
+        using namespace eon_host;
+        AirRef a;
+        a.prog = prog;
+        a.publics = publics;
+        a.n_public = n_public;
+        OpeningScope os(pcs);
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::from_abi(*alpha), Fr::from_abi(*zeta), 0, shard, nullptr,
+                        nullptr, nullptr, cc, os.get());
+        os.done(false);
+        copy_out(p, out);
+    });
+}
+
+int eon_prove_air_sharded_fs(eon_kzg_pcs* pcs, const eon_air_program* prog, const eon_fr* trace, uint64_t height,
+                             const eon_fr* publics, uint32_t n_public, eon_challenger* challenger,
+                             const eon_collective* shard, eon_proof* out, eon_fr* alpha_out, eon_fr* zeta_out) {
+    if (!pcs || !pcs->pcs || !prog || !trace || !challenger || !out || (n_public && !publics)) return EON_E_ARG;
+    if (!proof_arrays_ok(out)) return EON_E_ARG;
+    return guarded_prove(pcs, [&](eon_host::ConstraintCheck* cc) {
+        using namespace eon_host;
+        AirRef a;
+        a.prog = prog;
+        a.publics = publics;
+        a.n_public = n_public;
+        OpeningScope os(pcs);
+        Proof p = prove(*pcs->pcs, a, trace, height, Fr::zero(), Fr::zero(), 0, shard, &challenger->ch, nullptr,
+                        nullptr, cc, os.get());
+        os.done(true);
+        copy_out(p, out);
+        if (alpha_out) *alpha_out = p.alpha.abi();
+        if (zeta_out) *zeta_out = p.zeta.abi();
+    });
+}
+
 int eon_setup_preprocessed(eon_kzg_pcs* pcs, const eon_fr* pre_trace, uint64_t height, uint32_t width,
                            eon_preprocessed** out) {
     if (!pcs || !pcs->pcs) return EON_E_ARG;

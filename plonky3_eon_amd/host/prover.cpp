@@ -13,10 +13,19 @@
 // its own columns, and its folder accumulator times alpha^(K (VL - l1)) is its exact share of the
 // full one (folder.rs:81-85).  The partials are all-gathered (Q x 32 B, the one data-path
 // exchange) and combined on device; the per-column results are all-gathered at the end.
+//
+// Column sharding: a generic AIR's constraints read every column of a row, so a rank
+// that owns a column range (eon_shard_column_range) commits, extends and opens its columns, but
+// cannot evaluate the quotient on them alone.  The ranks exchange their extended columns once as
+// row blocks (eon_shard_pack_rows_dev, all_to_all, eon_shard_unpack_cols_dev): rank r then holds
+// every column of ITS rows of the quotient domain (eon_shard_row_range) plus the 2^log_qd rows its
+// "next" rows reach into, evaluates the quotient there (eon_quotient_values_rows_dev), and the row
+// blocks are all-gathered.  From there the tail is the lane-sharded one.
 #include "prover.h"
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +51,11 @@ constexpr uint32_t RECORD = 32;
 void all_gather(eon_ctx* ctx, const eon_collective* coll, const void* send, void* recv, uint64_t bytes) {
     const int rc = coll->all_gather(coll->user, send, recv, bytes, eon_ctx_stream(ctx));
     if (rc != 0) throw Error(EON_E_DEVICE, "collective all_gather failed (" + std::to_string(rc) + ")");
+}
+
+void all_to_all(eon_ctx* ctx, const eon_collective* coll, const void* send, void* recv, uint64_t bytes) {
+    const int rc = coll->all_to_all(coll->user, send, recv, bytes, eon_ctx_stream(ctx));
+    if (rc != 0) throw Error(EON_E_DEVICE, "collective all_to_all failed (" + std::to_string(rc) + ")");
 }
 
 void hip_ok(hipError_t e, const char* what) {
@@ -108,14 +122,43 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     if (air.n_public && !air.publics) throw Error(EON_E_ARG, "null public values");
     if (air.p2 && air.n_public) throw Error(EON_E_SHAPE, "the Poseidon2-AIR has no public values");
     if (air.p2) constraint_check = nullptr;  // the fused path has no program to check
-    const uint32_t width = air.width();
+    uint32_t width = air.width();  // of `trace`: the AIR's, or (column-sharded) the rank's range
     const uint32_t local_vl = air.p2 ? eon_p2air_vector_len(air.p2) : 1;
     const uint32_t k_lane = air.p2 ? eon_p2air_constraints_per_perm(air.p2) : 0;
     if (shard && shard->world <= 1) shard = nullptr;
     if (shard && (!shard->all_gather || shard->rank >= shard->world))
         throw Error(EON_E_ARG, "invalid collective");
-    if (shard && !air.p2) throw Error(EON_E_ARG, "lane sharding needs the (vectorized) Poseidon2-AIR");
     const uint32_t world = shard ? shard->world : 1, rank = shard ? shard->rank : 0;
+    // A program is sharded by columns.  What it cannot do is refused here, from arguments that are
+    // the same on every rank and before the first collective call, so no rank is left waiting.
+    const bool col_shard = shard && air.prog;
+    const uint32_t full_width = col_shard ? width : width * world;
+    if (col_shard) {
+        if (!shard->all_to_all) throw Error(EON_E_ARG, "the column-sharded prove needs a collective with all_to_all");
+        if (world > full_width)
+            throw Error(EON_E_ARG, "column sharding: more ranks than columns (" + std::to_string(world) + " ranks, " +
+                                       std::to_string(full_width) + " columns)");
+        if (pp || eon_air_program_preprocessed_width(air.prog) > 0)
+            throw Error(EON_E_ARG, "preprocessed columns are not column-sharded: prove on one device");
+        if (lookups || eon_air_program_permutation_width(air.prog) > 0)
+            throw Error(EON_E_ARG, "lookups are not column-sharded: prove on one device");
+        if (constraint_check)
+            throw Error(EON_E_ARG, "check_constraints is not column-sharded: it reads whole rows of the trace; "
+                                   "switch it off or prove on one device");
+        uint32_t col0 = 0;  // `trace` is the slice itself: its first column's position is the records' business
+        if (eon_shard_column_range(full_width, world, rank, &col0, &width) != EON_OK)
+            throw Error(EON_E_ARG, "eon_shard_column_range");
+    }
+    // columns of rank g in the full proof, and the (padded) per-rank slot count of the exchanges
+    auto cols_of = [&](uint32_t g, uint32_t* c0, uint32_t* wl) {
+        if (!col_shard) {
+            *c0 = g * width;
+            *wl = width;
+        } else if (eon_shard_column_range(full_width, world, g, c0, wl) != EON_OK) {
+            throw Error(EON_E_ARG, "eon_shard_column_range");
+        }
+    };
+    const uint32_t slots = col_shard ? (full_width + world - 1) / world : width;
     const uint32_t vector_len = local_vl * world;
     const uint32_t log_n = 63 - __builtin_clzll(height);
     // the preprocessed data against the AIR's declaration (prover.rs:58-88: the reference panics)
@@ -179,13 +222,23 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     std::vector<eon_g1_affine> full_commit;
     if (challenger) {
         if (shard) {
-            const uint64_t bytes = (uint64_t)width * sizeof(eon_g1_affine);
+            // padded slots (column ranges differ by one), trimmed to the full width in rank order
+            const uint64_t bytes = (uint64_t)slots * sizeof(eon_g1_affine);
             DeviceBuffer send(bytes), recv(bytes * world);
-            hip_ok(hipMemcpyAsync(send.get(), trace_commit[0].data(), bytes, hipMemcpyHostToDevice, st), "commit");
+            if (slots != width) hip_ok(hipMemsetAsync(send.get(), 0, bytes, st), "commit");
+            hip_ok(hipMemcpyAsync(send.get(), trace_commit[0].data(), (uint64_t)width * sizeof(eon_g1_affine),
+                                  hipMemcpyHostToDevice, st),
+                   "commit");
             all_gather(ctx, shard, send.get(), recv.get(), bytes);
-            full_commit.resize((uint64_t)width * world);
-            hip_ok(hipMemcpyAsync(full_commit.data(), recv.get(), bytes * world, hipMemcpyDeviceToHost, st), "commit");
+            std::vector<eon_g1_affine> all((uint64_t)slots * world);
+            hip_ok(hipMemcpyAsync(all.data(), recv.get(), bytes * world, hipMemcpyDeviceToHost, st), "commit");
             hip_ok(hipStreamSynchronize(st), "commit");
+            full_commit.resize(full_width);
+            for (uint32_t g = 0; g < world; g++) {
+                uint32_t c0, wl;
+                cols_of(g, &c0, &wl);
+                std::copy_n(all.begin() + (uint64_t)g * slots, wl, full_commit.begin() + c0);
+            }
         } else {
             full_commit = trace_commit[0];
         }
@@ -204,8 +257,30 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         });
     }
     // the trace LDE (prover.rs:315) while the host thread runs the transcript up to alpha
+    DeviceMatrix window;   // column-sharded: every column of this rank's quotient rows
+    double window_ms = 0;  // the window exchange, counted in EON_STAGE_EXCHANGE, not in the LDE
+    const uint64_t next_step = 1ull << log_qd;
+    const uint64_t block_rows = (q_rows + world - 1) / world;  // R: quotient rows per rank
     try {
         lde = pcs.get_evaluations_on_domain(trace_data, 0, quotient_domain);
+        if (col_shard) {
+            // rows of my columns -> columns of my rows: block h of `send` is the window of rank h
+            auto x0 = tick();
+            const uint64_t win_rows = block_rows + next_step;
+            const uint64_t block_bytes = win_rows * slots * sizeof(eon_fr);
+            DeviceBuffer send(block_bytes * world), recv(block_bytes * world);
+            check(ctx, eon_shard_pack_rows_dev(ctx, lde.data(), q_rows, full_width, world, rank, next_step,
+                                               send.as<eon_fr>()),
+                  "pack window rows");
+            check(ctx, eon_ctx_synchronize(ctx), "pack window rows");
+            lde = DeviceMatrix();  // back to the buffer cache: the window is 1/world of it, plus 2^log_qd rows
+            all_to_all(ctx, shard, send.get(), recv.get(), block_bytes);
+            window = DeviceMatrix::alloc(win_rows, full_width);
+            check(ctx, eon_shard_unpack_cols_dev(ctx, recv.as<eon_fr>(), q_rows, full_width, world, next_step,
+                                                 window.mutable_data()),
+                  "unpack window columns");
+            window_ms = ms(x0, tick());
+        }
         // recomputed each prove, as the reference does (prover.rs:321-322)
         if (pp) pre_lde = pcs.get_evaluations_on_domain(pp->data, 0, quotient_domain);
     } catch (...) {
@@ -260,11 +335,25 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         }
         perm_lde = pcs.get_evaluations_on_domain(perm_data, 0, quotient_domain);
     }
-    DeviceMatrix qv = DeviceMatrix::alloc(q_rows, 1);
+    DeviceMatrix qv = col_shard ? DeviceMatrix() : DeviceMatrix::alloc(q_rows, 1);
     {
         t2 = tick();
         const eon_fr a = alpha.abi();
-        if (air.p2)
+        if (col_shard) {
+            // this rank's block of quotient rows, in a slot of R rows (the last ranks' may be short
+            // or empty: the padding is zero and is trimmed after the all-gather)
+            uint64_t row0 = 0, n_rows = 0;
+            if (eon_shard_row_range(q_rows, world, rank, &row0, &n_rows) != EON_OK)
+                throw Error(EON_E_ARG, "eon_shard_row_range");
+            DeviceMatrix part = DeviceMatrix::alloc(block_rows, 1);
+            if (n_rows < block_rows)
+                hip_ok(hipMemsetAsync(part.mutable_data(), 0, block_rows * sizeof(eon_fr), st), "quotient block");
+            check(ctx,
+                  eon_quotient_values_rows_dev(ctx, air.prog, window.data(), log_n, log_qd, row0, n_rows, &a,
+                                               air.publics, air.n_public, part.mutable_data()),
+                  "quotient_values (rows)");
+            qv = std::move(part);
+        } else if (air.p2)
             check(ctx, eon_p2air_quotient_values_dev(ctx, air.p2, lde.data(), log_n, log_qd, &a, qv.mutable_data()),
                   "quotient_values");
         else if (perm_width > 0) {
@@ -290,8 +379,17 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
     lde = DeviceMatrix();  // back to the buffer cache before the opening
     pre_lde = DeviceMatrix();
     perm_lde = DeviceMatrix();
+    window = DeviceMatrix();
     auto t3 = tick();
-    if (shard) {
+    if (col_shard) {
+        // the row blocks in rank order are the quotient itself: rank r's slot starts at row r R
+        DeviceBuffer parts(sizeof(eon_fr) * block_rows * world);
+        all_gather(ctx, shard, qv.data(), parts.get(), sizeof(eon_fr) * block_rows);
+        qv = DeviceMatrix::alloc(q_rows, 1);
+        hip_ok(hipMemcpyAsync(qv.mutable_data(), parts.get(), sizeof(eon_fr) * q_rows, hipMemcpyDeviceToDevice, st),
+               "quotient blocks");
+        (void)tick();
+    } else if (shard) {
         DeviceBuffer parts(sizeof(eon_fr) * q_rows * world);
         all_gather(ctx, shard, qv.data(), parts.get(), sizeof(eon_fr) * q_rows);
         std::vector<eon_fr> w(world);
@@ -387,6 +485,11 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
             batched->delta_used = challenger->sample();
         }
     } else {
+        // The opening-bases collectives inside `open` are keyed by (height, point), in order of first
+        // use.  The trace round comes first and every rank has at least one trace column (lanes; a
+        // column range is never empty: world <= W), so every rank builds (N, zeta) and (N, zeta h)
+        // -- the quotient chunks have N rows too and are opened at zeta, a key already there.  A
+        // rank without a quotient chunk therefore issues exactly the collective calls of the others.
         CollectiveScope scope(ctx, shard);
         opened = pcs.open(rounds);  // prover.rs:424-442
     }
@@ -445,7 +548,8 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         }
     } else {
         // every rank's columns land at their global positions (rank order = lane order)
-        std::vector<uint64_t> rec((uint64_t)width * RECORD);
+        // (slots of `slots` columns: column ranges differ by one, the padding is zero)
+        std::vector<uint64_t> rec((uint64_t)slots * RECORD, 0);
         for (uint32_t c = 0; c < width; c++) {
             uint64_t* r = rec.data() + (uint64_t)c * RECORD;
             std::memcpy(r, &trace_commit[0][c], 64);
@@ -461,30 +565,33 @@ Proof prove(KzgPcs& pcs, const AirRef& air, const eon_fr* trace, uint64_t height
         std::vector<uint64_t> all(rec.size() * world);
         hip_ok(hipMemcpyAsync(all.data(), recv.get(), bytes * world, hipMemcpyDeviceToHost, st), "records");
         hip_ok(hipStreamSynchronize(st), "records");
-        const uint64_t full = (uint64_t)width * world;
-        proof.trace_commit.resize(full);
+        proof.trace_commit.resize(full_width);
         for (int p = 0; p < 2; p++) {
-            proof.trace_opened[p].resize(full);
-            proof.trace_witnesses[p].resize(full);
+            proof.trace_opened[p].resize(full_width);
+            proof.trace_witnesses[p].resize(full_width);
         }
-        for (uint64_t c = 0; c < full; c++) {
-            const uint64_t* r = all.data() + c * RECORD;
-            std::memcpy(&proof.trace_commit[c], r, 64);
-            std::memcpy(&proof.trace_opened[0][c], r + 8, 32);
-            std::memcpy(&proof.trace_opened[1][c], r + 12, 32);
-            std::memcpy(&proof.trace_witnesses[0][c], r + 16, 64);
-            std::memcpy(&proof.trace_witnesses[1][c], r + 24, 64);
+        for (uint32_t g = 0; g < world; g++) {
+            uint32_t c0, wl;
+            cols_of(g, &c0, &wl);
+            for (uint32_t k = 0; k < wl; k++) {
+                const uint64_t* r = all.data() + ((uint64_t)g * slots + k) * RECORD;
+                const uint64_t c = (uint64_t)c0 + k;
+                std::memcpy(&proof.trace_commit[c], r, 64);
+                std::memcpy(&proof.trace_opened[0][c], r + 8, 32);
+                std::memcpy(&proof.trace_opened[1][c], r + 12, 32);
+                std::memcpy(&proof.trace_witnesses[0][c], r + 16, 64);
+                std::memcpy(&proof.trace_witnesses[1][c], r + 24, 64);
+            }
         }
     }
     auto t6 = tick();
     proof.stage_ms[EON_STAGE_COMMIT_TRACE] = ms(t0, t1);
-    proof.stage_ms[EON_STAGE_TRACE_LDE] = ms(t1, t2);
+    proof.stage_ms[EON_STAGE_TRACE_LDE] = ms(t1, t2) - window_ms;
     proof.stage_ms[EON_STAGE_QUOTIENT] = ms(t2, t3);
-    proof.stage_ms[EON_STAGE_EXCHANGE] = ms(t3, t3x);
+    proof.stage_ms[EON_STAGE_EXCHANGE] = ms(t3, t3x) + window_ms;  // both data exchanges
     proof.stage_ms[EON_STAGE_COMMIT_QUOTIENT] = ms(t3x, t4);
     proof.stage_ms[EON_STAGE_OPEN] = ms(t4, t5);
     proof.stage_ms[EON_STAGE_ASSEMBLE] = ms(t5, t6);
-    (void)rank;
     return proof;
 }
 

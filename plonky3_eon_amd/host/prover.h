@@ -92,8 +92,11 @@ struct AirRef {
     uint32_t width() const;
 };
 
-// `trace`: this rank's height x width(air) device trace.  With `shard` (world > 1, Poseidon2 only)
-// the AIR is the rank's lane range; every rank returns the full proof.  With `challenger`, alpha
+// `trace`: this rank's height x width(air) device trace.  With `shard` (world > 1) every rank
+// returns the full proof: of the Poseidon2-AIR the AIR is the rank's lane range; of a program
+// `trace` is the rank's height x wl column range (eon_shard_column_range) of the program's full
+// width (prover.cpp: column sharding; main trace and public values only -- preprocessed columns,
+// lookups, the constraint check and the batched opening are EON_E_ARG with a collective).  With `challenger`, alpha
 // and zeta are sampled from it (prover.rs:196-208, 300, 373, 416) and the inputs are ignored.
 // max_constraint_degree is the Poseidon2-AIR's (3); a program carries its own.  `preprocessed`
 // (programs only, no sharding) is required exactly when the program has preprocessed columns: it is

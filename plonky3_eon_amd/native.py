@@ -107,6 +107,10 @@ SIGNATURES = {
                                   ctypes.POINTER(eon_proof), _P, _P]),
     "eon_prove_air": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_proof)]),
     "eon_prove_air_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, ctypes.POINTER(eon_proof), _P, _P]),
+    "eon_prove_air_sharded": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, _P, ctypes.POINTER(eon_collective),
+                                     ctypes.POINTER(eon_proof)]),
+    "eon_prove_air_sharded_fs": (_INT, [_P, _P, _P, _U64, _P, _U32, _P, ctypes.POINTER(eon_collective),
+                                        ctypes.POINTER(eon_proof), _P, _P]),
     "eon_setup_preprocessed": (_INT, [_P, _P, _U64, _U32, ctypes.POINTER(_P)]),
     "eon_preprocessed_destroy": (None, [_P]),
     "eon_preprocessed_info": (_INT, [_P, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
@@ -937,8 +941,15 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
                  delta: int | None = None) -> Proof:
     """prover.prove through the C++ driver.  `air` is a Poseidon2Air (fused quotient kernel) or an
     air.AirProgram (any AIR, with `public_values`: canonical ints).  `trace`: (N, width, 4) device
-    tensor; with a collective (world > 1, Poseidon2 only) `air`/`trace` are this rank's lanes and
-    the proof is the full one.  With `challenger` (eon_prove_*_fs) alpha and zeta are sampled from
+    tensor.  With a collective (world > 1; TorchCollective or RcclCollective) every rank returns the
+    full proof, equal to the one-device proof byte for byte.  Of a Poseidon2Air, `air`/`trace` are
+    this rank's lanes.  An AirProgram is sharded by columns (eon_prove_air_sharded[_fs]): rank g
+    owns the columns distributed.column_range(air.width, world, g), and `trace` is either that slice,
+    (N, wl, 4), or the full (N, width, 4) trace, from which the rank's columns are copied out; any
+    other width is a ValueError, more ranks than columns an EonError(EON_E_ARG) on every rank.  The
+    ranks exchange their extended columns once as row blocks, each evaluates the quotient on its own
+    rows, and the rest is sharded as for the lanes.  Preprocessed columns, lookups, the
+    check_constraints switch and the batched opening are refused with a collective.  With `challenger` (eon_prove_*_fs) alpha and zeta are sampled from
     the transcript and returned in proof.alpha / proof.zeta (canonical ints); the arguments are
     ignored.  With `preprocessed` (setup_preprocessed; generic AIRs only) the proof carries its
     commitment and a third Opened entry, the preprocessed columns at zeta and zeta * h.  An
@@ -960,11 +971,13 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         raise ValueError(f"opening must be one of {sorted(OPENING_MODES)}, not {opening!r}")
     batched = opening == "batched"
     if batched and collective is not None and collective.c.world > 1:
-        raise ValueError("the batched opening is not lane-sharded: prove without a collective")
+        raise ValueError("the batched opening is not sharded: prove without a collective")
 
     generic = isinstance(air, AirProgram)
     world = collective.c.world if collective is not None else 1
-    w = air.width * world
+    # a program is sharded by columns (its width is the full one), the Poseidon2-AIR by lanes
+    col_shard = generic and world > 1
+    w = air.width if generic else air.width * world
     log_qd = air.log_quotient_degree() if generic else log_quotient_degree(max_constraint_degree)
     chunks = 1 << log_qd
     tc = np.zeros((w, 8), np.uint64)
@@ -976,7 +989,7 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     out = eon_proof(_p(tc), _p(qc), _p(to), _p(tw), _p(qo), _p(qw), 0)
     if preprocessed is not None:
         if not generic or collective is not None:
-            raise ValueError("preprocessed columns need an AirProgram and no collective")
+            raise ValueError("preprocessed columns need an AirProgram and no collective (they are not sharded)")
         wp = preprocessed.width
         pc = np.zeros((wp, 8), np.uint64)
         po = np.zeros((2, wp, 4), np.uint64)
@@ -986,7 +999,7 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
     lookups = generic and air.permutation_width > 0
     if lookups:
         if collective is not None:
-            raise ValueError("lookups are not lane-sharded")
+            raise ValueError("lookups are not sharded: prove without a collective")
         wq = air.permutation_width
         mc = np.zeros((wq, 8), np.uint64)
         mo = np.zeros((2, wq, 4), np.uint64)
@@ -997,7 +1010,19 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
         out = out_lk.pp.base
     elif permutation_challenges is not None or preprocessed_trace is not None:
         raise ValueError("permutation_challenges / preprocessed_trace need an AirProgram with lookups")
-    t = trace.contiguous()
+    t = trace
+    if col_shard:
+        from .distributed import column_range
+
+        if generic and pcs.check_constraints:
+            raise ValueError("check_constraints is not column-sharded: switch it off or prove without a collective")
+        c0, wl = column_range(air.width, world, collective.c.rank)
+        if t.shape[1] == air.width:  # the full trace (also when wl == width cannot be: world > 1)
+            t = t[:, c0:c0 + wl]
+        elif t.shape[1] != wl:
+            raise ValueError(f"the trace has {t.shape[1]} columns: rank {collective.c.rank} of {world} takes its "
+                             f"slice of {wl} columns or the full width {air.width}")
+    t = t.contiguous()
     import torch
 
     torch.cuda.synchronize(t.device)  # the trace was produced on torch's stream
@@ -1034,6 +1059,9 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
                 pcs.check(pcs.lib.eon_prove_air_pp(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
                                                    preprocessed.handle, ctypes.byref(a), ctypes.byref(z),
                                                    ctypes.byref(out_pp)))
+            elif col_shard:
+                pcs.check(pcs.lib.eon_prove_air_sharded(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                                        ctypes.byref(a), ctypes.byref(z), coll, ctypes.byref(out)))
             elif generic:
                 pcs.check(pcs.lib.eon_prove_air(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub, ctypes.byref(a),
                                                 ctypes.byref(z), ctypes.byref(out)))
@@ -1046,9 +1074,11 @@ def prove_native(air, pcs: NativeKzgPcs, trace, alpha: int | None, zeta: int | N
                 pcs.check(pcs.lib.eon_prove_air_pp_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
                                                       preprocessed.handle, challenger.handle, ctypes.byref(out_pp),
                                                       _p(a_out), _p(z_out)))
+            elif col_shard:
+                pcs.check(pcs.lib.eon_prove_air_sharded_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
+                                                           challenger.handle, coll, ctypes.byref(out), _p(a_out),
+                                                           _p(z_out)))
             elif generic:
-                if collective is not None:
-                    raise ValueError("the generic AIR path is not lane-sharded")
                 pcs.check(pcs.lib.eon_prove_air_fs(pcs._h, air.handle, tp, int(t.shape[0]), _p(pub), npub,
                                                    challenger.handle, ctypes.byref(out), _p(a_out), _p(z_out)))
             else:
